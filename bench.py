@@ -1,6 +1,14 @@
 """Benchmark: device-resident bloom build + probe (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|c5|sst] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c1|c3|c4|c5|sst] [--full]
+                    [--dump-outputs DIR] [--no-cpu-baseline]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds, after
+the timed steps, everything else the line can carry: the correctness checks of the measured
+state, the host-inclusive legs, the CPU baselines, the comparison and per-call latency legs (the
+--no-* options switch single legs off again).  --dump-outputs DIR writes what the last timed
+step computed as DIR/<name>.npy (dump_outputs); the inputs are generated from fixed seeds, so
+two builds of the library can be compared output for output.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N ranks itself (one
 child process per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, 127.0.0.1 rendezvous) before
@@ -54,6 +62,15 @@ def parse():
     ap.add_argument("--c5-probes", type=int, default=100_000_000, help="c5: probe keys (reference 100M)")
     ap.add_argument("--build-mode", type=int, default=0, help="0 auto, 1 atomic, 2 tiled")
     ap.add_argument("--probe-mode", type=int, default=0, help="0 auto, 1 direct, 2 tiled")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the checks of the "
+                         "measured state, CPU baselines, host-inclusive legs, comparison and latency legs (each can "
+                         "still be switched off with its --no-* option); without it a run sets up, warms up, times "
+                         "the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (bitmaps, hit masks, encoded "
+                         "blocks) as DIR/<name>.npy, float32, at most 64 MB in all (larger arrays: a fixed seeded "
+                         "sample plus block popcounts over the whole array)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-events", action="store_true", help="diagnostic: time without per-step HIP events")
     ap.add_argument("--no-host-inclusive", action="store_true", help="skip the pinned host<->device leg")
@@ -149,6 +166,47 @@ def algorithmic_bytes(n, L, k, m_bits, offsets):
 
 def probe_bytes(n, L, k, offsets):
     return n * L + 4 * n * k + n // 8 + (8 * n if offsets else 0)
+
+
+DUMP_BUDGET_BYTES = 48 * 2 ** 20  # of the 64 MB --dump-outputs may write
+DUMP_SEED = 0xD0
+
+
+def dump_outputs(directory: str, arrays: dict, np, rank: int = 0) -> dict:
+    """--dump-outputs: write the byte arrays the last timed step left (`arrays`: name -> (size in
+    bytes, function returning them as a uint8 numpy array; called one at a time)) as float32 .npy
+    files, every byte one exact value.  The budget is shared smallest first: an array within its
+    share goes out whole as <name>.npy; a larger one as <name>_sample.npy (its bytes at positions
+    drawn once from a generator seeded by DUMP_SEED and the array's size, ascending, so two builds
+    sample the same positions) and <name>_popcount.npy (set bits per block of equal length over the
+    whole array: a difference anywhere shows).  Returns what was written, for the result line."""
+    os.makedirs(directory, exist_ok=True)
+    suffix = f"_rank{rank}" if rank else ""
+    left = DUMP_BUDGET_BYTES // 4
+    todo = sorted(arrays, key=lambda nm: (arrays[nm][0], nm))
+    bits8 = np.unpackbits(np.arange(256, dtype=np.uint8)[:, None], axis=1).sum(axis=1).astype(np.uint8)
+    written = {}
+    for i, name in enumerate(todo):
+        size, get = arrays[name]
+        share = left // (len(todo) - i)
+        a = np.ascontiguousarray(get()).view(np.uint8).reshape(-1)
+        assert a.size == size, (name, a.size, size)
+        if size <= share:
+            np.save(os.path.join(directory, f"{name}{suffix}.npy"), a.astype(np.float32))
+            left -= size
+            written[name + suffix] = {"bytes": size, "whole": True}
+            continue
+        nblk = min(65_536, share // 16)
+        ns = share - nblk
+        idx = np.sort(np.random.default_rng([DUMP_SEED, size]).integers(0, size, ns))
+        np.save(os.path.join(directory, f"{name}_sample{suffix}.npy"), a[idx].astype(np.float32))
+        blk = -(-size // nblk)  # bytes per block; the last one may be short
+        counts = np.add.reduceat(bits8[a], np.arange(0, size, blk), dtype=np.int64)
+        np.save(os.path.join(directory, f"{name}_popcount{suffix}.npy"), counts.astype(np.float32))
+        left -= ns + len(counts)
+        written[name + suffix] = {"bytes": size, "whole": False, "sampled": int(ns), "popcount_block_bytes": int(blk)}
+        del a
+    return written
 
 
 def measured_traffic(config: str) -> dict | None:
@@ -708,10 +766,20 @@ def sets_main(args, rank, world, local, torch, dist, np):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     pass_ms = sum(e[i][0].elapsed_time(e[i][1]) for e in events for i in range(nev)) / (args.steps * nev)
-    # correctness on the measured state
-    ok = True
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step left its caller: c4 every filter's bitmap, c5 every filter's hit mask
+        if args.config == "c4":
+            arrays = {f"bitmap_{g}": (nb_bytes, lambda g=g: np.frombuffer(filters[g].bitmap(), dtype=np.uint8))
+                      for g in mine}
+        else:
+            arrays = {f"hit_mask_{g}": (hms[g].numel(), lambda g=g: hms[g].cpu().numpy()) for g in mine}
+        dumped = dump_outputs(args.dump_outputs, arrays, np, rank)
+    # correctness on the measured state (--full)
+    ok = None
     fp_rate = None
-    if args.config == "c4":
+    fp_ok = None
+    if args.full and args.config == "c4":
         g = mine[0]
         bf = filters[g]
         hm = torch.zeros((n + 7) // 8, dtype=torch.uint8, device="cuda")
@@ -725,7 +793,8 @@ def sets_main(args, rank, world, local, torch, dist, np):
         bf.probe_device_fixed(absent.data_ptr(), 16, 1_000_000, hm2.data_ptr())
         bf.sync()
         fp_rate = float(np.unpackbits(hm2.cpu().numpy()).sum()) / 1e6
-    else:
+    elif args.full:
+        ok = True
         fp_total, fp_expect = 0, 0.0
         n_abs = max(0, qb - max(qa, half))  # the rank's absent keys
         for g in mine:
@@ -740,13 +809,14 @@ def sets_main(args, rank, world, local, torch, dist, np):
             fp_expect += n_abs * fill ** k
         fp_ok = fp_total <= 3 * fp_expect + 20 * len(mine)
     host_c5 = None
-    if args.config == "c5" and not args.no_host_c5:
+    if args.full and args.config == "c5" and not args.no_host_c5:
         host_c5 = c5_host_resident(args, filters, mine, hms, q, nq, k, torch, np, L)
     if world > 1:
         elapsed = float(all_reduce_scalar(torch, dist, elapsed, dist.ReduceOp.MAX, torch.float64))
-        ok = bool(all_reduce_scalar(torch, dist, 1 if ok else 0, dist.ReduceOp.MIN, torch.int32))
-        if args.config == "c5":
-            fp_ok = bool(all_reduce_scalar(torch, dist, 1 if fp_ok else 0, dist.ReduceOp.MIN, torch.int32))
+        if args.full:
+            ok = bool(all_reduce_scalar(torch, dist, 1 if ok else 0, dist.ReduceOp.MIN, torch.int32))
+            if args.config == "c5":
+                fp_ok = bool(all_reduce_scalar(torch, dist, 1 if fp_ok else 0, dist.ReduceOp.MIN, torch.int32))
     if rank == 0:
         ms = elapsed / args.steps * 1e3
         if args.config == "c4":
@@ -790,9 +860,12 @@ def sets_main(args, rank, world, local, torch, dist, np):
                          "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic, "kernel": pk,
                          "algorithmic_bytes": int(b_pass), "avg_ms": round(pass_ms, 4),
                          "traffic_source": tr["source"] if tr else None},
-            "check": {"members_all_hit": ok},
             **dist_report(dist, world),
         }
+        if args.full:
+            out["check"] = {"members_all_hit": ok}
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if sim:
             out["simulated_rank"] = {"rank": args.sim_rank, "world": args.sim_world,
                                      "note": "one rank's share of a --sim-world job on this GPU; value = that "
@@ -800,18 +873,19 @@ def sets_main(args, rank, world, local, torch, dist, np):
         if fp_rate is not None:
             out["check"]["fp_rate_1M_absent"] = fp_rate
         if args.config == "c5":
-            out["check"].update({"false_positives_rank0": fp_total, "fp_expected_rank0": round(fp_expect, 1),
-                                 "fp_within_3x_expected": bool(fp_ok), "probe_detail": hex(s0.last_probe_detail)})
+            if args.full:
+                out["check"].update({"false_positives_rank0": fp_total, "fp_expected_rank0": round(fp_expect, 1),
+                                     "fp_within_3x_expected": bool(fp_ok), "probe_detail": hex(s0.last_probe_detail)})
             if host_c5 is not None:
                 out["host_resident"] = host_c5
             if replication is not None:
                 # one-time: the layout's filters arrive once, then every step probes them
                 replication["built_here"] = own
                 out["replication"] = replication
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = c5_cpu_baseline(args, filters, mine, hms, q, n_f, nb_bytes, k, np)
                 out["check"]["oracle_sample_equal"] = out["cpu_baseline"].pop("oracle_sample_equal")
-        if args.config == "c5" and not args.no_compare:
+        if args.full and args.config == "c5" and not args.no_compare:
             # the same work as independent single-filter probes (no shared partition)
             tq = []
             for _ in range(2):
@@ -892,21 +966,30 @@ def mixed_main(args, rank, world, local, torch, dist, np):
             el = float(all_reduce_scalar(torch, dist, el, dist.ReduceOp.MAX, torch.float64))
         return el / args.steps * 1e3, sum(a.elapsed_time(b) for a, b in evs) / args.steps
 
-    ms_pf, _ = timed(per_filter)
-    got_pf = {g: hms[g].cpu().numpy().copy() for g in mine}
+    if args.full:
+        # the comparison leg: one probe pipeline per filter, timed the same way, and its hit masks
+        ms_pf, _ = timed(per_filter)
+        got_pf = {g: hms[g].cpu().numpy().copy() for g in mine}
     ms, pass_ms = timed(fused)
-    got = {g: hms[g].cpu().numpy() for g in mine}
-    ok = all(np.array_equal(got[g], got_pf[g]) for g in mine)
-    fp_total, fp_expect = 0, 0.0
-    for g in mine:
-        bits = np.unpackbits(got[g], bitorder="little")[:nq]
-        ok &= bool(bits[starts[g]:starts[g] + ns[g]].all())
-        fill = filters[g].popcount() / (8 * filters[g].nb_bytes)
-        fp_total += int(bits[total:].sum())
-        fp_expect += total * fill ** k
-    fp_ok = fp_total <= 3 * fp_expect + 20 * len(mine)
-    if world > 1:
-        ok = bool(all_reduce_scalar(torch, dist, 1 if ok else 0, dist.ReduceOp.MIN, torch.int32))
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step returned to its caller: every filter's hit mask
+        dumped = dump_outputs(args.dump_outputs,
+                              {f"hit_mask_{g}": (hms[g].numel(), lambda g=g: hms[g].cpu().numpy()) for g in mine},
+                              np, rank)
+    if args.full:
+        got = {g: hms[g].cpu().numpy() for g in mine}
+        ok = all(np.array_equal(got[g], got_pf[g]) for g in mine)
+        fp_total, fp_expect = 0, 0.0
+        for g in mine:
+            bits = np.unpackbits(got[g], bitorder="little")[:nq]
+            ok &= bool(bits[starts[g]:starts[g] + ns[g]].all())
+            fill = filters[g].popcount() / (8 * filters[g].nb_bytes)
+            fp_total += int(bits[total:].sum())
+            fp_expect += total * fill ** k
+        fp_ok = fp_total <= 3 * fp_expect + 20 * len(mine)
+        if world > 1:
+            ok = bool(all_reduce_scalar(torch, dist, 1 if ok else 0, dist.ReduceOp.MIN, torch.int32))
     if rank != 0:
         return
     # SURVEY.md §8d probe bytes with the key read once for the set: nq*L + nf*(4*nq*k + nq/8)
@@ -926,13 +1009,17 @@ def mixed_main(args, rank, world, local, torch, dist, np):
                      "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None,
                      "kernel": "k_probe_set (each key hashed once, every filter tested; bitmaps Infinity-Cache resident)",
                      "algorithmic_bytes": int(b_pass), "avg_ms": round(pass_ms, 4)},
-        "per_filter_pipelines_ms": round(ms_pf, 4), "speedup_vs_per_filter": round(ms_pf / ms, 2),
-        "check": {"members_all_hit": ok, "equal_to_per_filter_probes": ok, "false_positives": fp_total,
-                  "fp_expected": round(fp_expect, 1), "fp_within_3x_expected": bool(fp_ok),
-                  "probe_detail": hex(fl[0].last_probe_detail)},
         **dist_report(dist, world),
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full:
+        out.update({
+            "per_filter_pipelines_ms": round(ms_pf, 4), "speedup_vs_per_filter": round(ms_pf / ms, 2),
+            "check": {"members_all_hit": ok, "equal_to_per_filter_probes": ok, "false_positives": fp_total,
+                      "fp_expected": round(fp_expect, 1), "fp_within_3x_expected": bool(fp_ok),
+                      "probe_detail": hex(fl[0].last_probe_detail)}})
+    if args.full and world == 1 and not args.no_cpu_baseline:
         # the C oracle (OpenMP, all host cores) on a 2M-key sample against every filter, and the
         # sample's hit masks equal to the device's
         o = COracle()
@@ -956,14 +1043,14 @@ def sst_main(args, rank, world, local, torch, dist, np):
     SSTable per GPU — 3.5M records of a 16-B hex key and a 48-B value (72 B encoded, 252 MB of
     data blocks, the reference's 250 MB target), records and the host block plan already in
     HBM.  A step = one pbf_encode_data_blocks over every block.  value = records / s (all
-    ranks).  Also: the host-inclusive SSTable build from Python lists (pack, plan, H2D, encode,
-    D2H, meta blocks, device bloom) on a 1M-record sample, and the oracle restatement of the
+    ranks).  With --full also (sst_host_legs): the host-inclusive SSTable build from Python lists
+    (pack, plan, H2D, encode, D2H, meta blocks, device bloom) on a 1M-record sample, and the oracle restatement of the
     reference's builder (oracle/sstable_oracle.py) on a bounded sample as the CPU baseline."""
     import ctypes
 
     from pebbledb_amd import _native
     from pebbledb_amd.keys import PackedKeys, splitmix_hex_keys
-    from pebbledb_amd.sstable_data import build_sstable, key_offsets, plan_blocks
+    from pebbledb_amd.sstable_data import key_offsets, plan_blocks
 
     n, vlen = 3_500_000, 48
     L = _native.lib()
@@ -1002,6 +1089,32 @@ def sst_main(args, rank, world, local, torch, dist, np):
     section = int(bo[-1])
     alg = pk.data.size + vals.size + 2 * 8 * (n + 1) + section  # read keys, values, offsets; write blocks
     ach = alg / (ms * 1e-3) / 1e9
+    out_line = {
+        "metric": "Mrecords/s SSTable data-block encode (device-resident), 3.5M x (16-B key, 48-B value)",
+        "value": round(n * world / (ms * 1e-3) / 1e6, 3), "unit": "Mrecords/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic (hex keys, random values)",
+        "config": {"workload": f"sst: {n} records, {nblocks} data blocks of <= 64 KiB, {section} B section per GPU",
+                   "parallelism": f"sstable-per-gpu x{world}"},
+        "roofline": {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None, "kernel": "k_encode_blocks",
+                     "algorithmic_bytes": int(alg), "avg_ms": round(ms, 4)},
+    }
+    if args.dump_outputs:
+        # what the last timed step returned to its caller: the encoded data-block section
+        out_line["dumped_outputs"] = dump_outputs(args.dump_outputs,
+                                                  {"data_section": (section, lambda: out.cpu().numpy())}, np, rank)
+    if args.full:
+        out_line.update(sst_host_legs(args, np, local, vals, vlen))
+    print(json.dumps(out_line), flush=True)
+
+
+def sst_host_legs(args, np, local, vals, vlen):
+    """--config sst --full: the host-inclusive SSTable build from Python lists and from the
+    memtable's encoded records, the compaction leg and the CPU baseline (sst_main's docstring), as
+    the result line's host_inclusive / flush_host_inclusive / compaction / cpu_baseline."""
+    from pebbledb_amd.keys import PackedKeys
+    from pebbledb_amd.sstable_data import build_sstable
     # host-inclusive SSTable file from Python lists, 1M records
     hn = 1_000_000
     hkeys = [format(x, "016x") for x in range(hn)]
@@ -1044,16 +1157,7 @@ def sst_main(args, rank, world, local, torch, dist, np):
         so.data_and_meta(hkeys[cn:cn + 20000], hvals[cn:cn + 20000], 65_536)
         cn += 20000
     tc = time.perf_counter() - tc
-    out_line = {
-        "metric": "Mrecords/s SSTable data-block encode (device-resident), 3.5M x (16-B key, 48-B value)",
-        "value": round(n * world / (ms * 1e-3) / 1e6, 3), "unit": "Mrecords/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic (hex keys, random values)",
-        "config": {"workload": f"sst: {n} records, {nblocks} data blocks of <= 64 KiB, {section} B section per GPU",
-                   "parallelism": f"sstable-per-gpu x{world}"},
-        "roofline": {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": None, "kernel": "k_encode_blocks",
-                     "algorithmic_bytes": int(alg), "avg_ms": round(ms, 4)},
+    return {
         "host_inclusive": {"records": hn, "s": round(th, 3), "Mrecords_s": round(hn / th / 1e6, 3),
                            "file_bytes": len(f), "what": "build_sstable(list[str], list[bytes]): pack, plan, H2D, "
                                                           "encode, D2H, meta blocks, device bloom, file assembly"},
@@ -1070,7 +1174,6 @@ def sst_main(args, rank, world, local, torch, dist, np):
                                    f"on {cn} records in {tc:.1f}s"},
         "compaction": compaction,
     }
-    print(json.dumps(out_line), flush=True)
 
 
 def compaction_leg(np, device, n=4_000_000, vlen=48, max_sstable_size=100_000_000, reps=3):
@@ -1312,17 +1415,30 @@ def main():
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     gpu_span_ms = span[0].elapsed_time(span[1])
-    # correctness guard on the measured data (the last step's hit mask): every member must hit
-    hm = hitmask.cpu().numpy()
-    members_ok = bool((np.unpackbits(hm, bitorder="little")[:n] == 1).all())
-    fp = int(np.unpackbits(hm, bitorder="little")[n:2 * n].sum())
-    # a corrupted bitmap (e.g. all ones) still lets every member hit: the absent half must show
-    # false positives at the filter's own rate, fill^k (fill measured on the device)
-    # positions a signed 32-bit hash can reach: all m, or 2^32 of them when m > 2^32
-    # (bloom_filter.py:47 floor-mod)
-    fill = bf.popcount() / min(m_bits, 2 ** 32)
-    fp_expect = n * fill ** k
-    fp_ok = fp <= 3 * fp_expect + 20
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step returned to its caller: the filter's bitmap and the hit mask
+        dumped = dump_outputs(args.dump_outputs, {
+            "bitmap": (nb_bytes, lambda: np.frombuffer(bf.bitmap(), dtype=np.uint8)),
+            "hit_mask": (hitmask.numel(), lambda: hitmask.cpu().numpy())}, np, rank)
+    check = None
+    if args.full:
+        # correctness guard on the measured data (the last step's hit mask): every member must hit
+        hm = hitmask.cpu().numpy()
+        members_ok = bool((np.unpackbits(hm, bitorder="little")[:n] == 1).all())
+        fp = int(np.unpackbits(hm, bitorder="little")[n:2 * n].sum())
+        # a corrupted bitmap (e.g. all ones) still lets every member hit: the absent half must show
+        # false positives at the filter's own rate, fill^k (fill measured on the device)
+        # positions a signed 32-bit hash can reach: all m, or 2^32 of them when m > 2^32
+        # (bloom_filter.py:47 floor-mod)
+        fill = bf.popcount() / min(m_bits, 2 ** 32)
+        fp_expect = n * fill ** k
+        fp_ok = fp <= 3 * fp_expect + 20
+        if world > 1:
+            members_ok = bool(all_reduce_scalar(torch, dist, 1 if members_ok else 0, dist.ReduceOp.MIN, torch.int32))
+            fp_ok = bool(all_reduce_scalar(torch, dist, 1 if fp_ok else 0, dist.ReduceOp.MIN, torch.int32))
+        check = {"members_all_hit": members_ok, "false_positives": fp, "probes_absent": n,
+                 "fp_expected": round(fp_expect, 2), "fp_within_3x_expected": bool(fp_ok)}
     if world > 1:
         dist.barrier()
     elapsed = t1 - t0
@@ -1342,11 +1458,9 @@ def main():
         quarters = [round(sum(per[i * q:(i + 1) * q]) / q, 4) for i in range(4)]
     if world > 1:
         elapsed = float(all_reduce_scalar(torch, dist, elapsed, dist.ReduceOp.MAX, torch.float64))
-        members_ok = bool(all_reduce_scalar(torch, dist, 1 if members_ok else 0, dist.ReduceOp.MIN, torch.int32))
-        fp_ok = bool(all_reduce_scalar(torch, dist, 1 if fp_ok else 0, dist.ReduceOp.MIN, torch.int32))
 
     host_inc = None
-    if rank == 0 and offs is None and not args.no_host_inclusive:
+    if args.full and rank == 0 and offs is None and not args.no_host_inclusive:
         host_inc = host_inclusive(bf, keys, n, nb_bytes, L, torch, np)
 
     if rank == 0:
@@ -1406,13 +1520,15 @@ def main():
             "roofline_probe": {"achieved": round(ach_probe, 1), "frac": round(ach_probe / HBM_PEAK_GBS, 4),
                                "algorithmic_bytes": int(b_probe), "traffic": int(traffic["probe"]) if traffic else None},
             "traffic_source": traffic["source"] if traffic else "no PMC summary for this library build",
-            "check": {"members_all_hit": members_ok, "false_positives": fp, "probes_absent": n,
-                      "fp_expected": round(fp_expect, 2), "fp_within_3x_expected": bool(fp_ok)},
             **dist_report(dist, world),
         }
+        if check is not None:
+            out["check"] = check
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if host_inc is not None:
             out["host_inclusive"] = host_inc
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(nb_bytes, k, kind, args.cpu_seconds)
             if args.config == "c1":
                 out["dropin_latency"] = dropin_latency(local)

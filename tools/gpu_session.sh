@@ -54,7 +54,7 @@ for step in "$@"; do
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
     pytest) run pytest 900 python -u -m pytest tests -m gpu -x -v -rf --timeout 150 --timeout-method thread ;;
     pytest_new) run pytest_new 600 python -u -m pytest ${PBF_TESTS:-tests/test_gpu_multi.py} -m gpu -x -v -rf --timeout 150 --timeout-method thread ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     benchq) for r in 1 2; do run benchq_$r 300 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-host-inclusive; done ;;
     prof) prof prof 600 --steps 20 --warmup 5 --no-cpu-baseline --no-host-inclusive ;;
     profq) prof profq 300 --steps 20 --warmup 5 --no-cpu-baseline --no-host-inclusive ;;
@@ -66,18 +66,18 @@ for step in "$@"; do
     pmc_c3) run pmc_c3 2400 tools/pmc_passes.sh gpurun_out/pmc_c3 --config c3 ;;
     pmc_c4) run pmc_c4 2400 tools/pmc_passes.sh gpurun_out/pmc_c4 --config c4 ;;
     pmc_c4s) PBF_STREAMS=1 run pmc_c4s 2400 tools/pmc_passes.sh gpurun_out/pmc_c4s --config c4 ;;
-    bench_c1) run bench_c1 300 python bench.py --config c1 --steps 50 --warmup 5 ;;
-    bench_c3) run bench_c3 600 python bench.py --config c3 --steps 5 --warmup 2 ;;
-    bench_c4) run bench_c4 600 python bench.py --config c4 --steps 3 --warmup 1 ;;
-    bench_c5) run bench_c5 600 python bench.py --config c5 --steps 5 --warmup 2 ;;
-    bench_c5mixed) run bench_c5mixed 600 python bench.py --config c5mixed --steps 5 --warmup 2 ;;
-    bench_sst) run bench_sst 600 python bench.py --config sst --steps 20 --warmup 3 ;;
-    others) run bench_c1 300 python bench.py --config c1 --steps 50 --warmup 5
-            run bench_c3 600 python bench.py --config c3 --steps 5 --warmup 2
-            run bench_c4 600 python bench.py --config c4 --steps 3 --warmup 1
-            run bench_c5 600 python bench.py --config c5 --steps 5 --warmup 2
-            run bench_c5mixed 600 python bench.py --config c5mixed --steps 5 --warmup 2
-            run bench_sst 600 python bench.py --config sst --steps 20 --warmup 3 ;;
+    bench_c1) run bench_c1 300 python bench.py --config c1 --steps 50 --warmup 5 --full ;;
+    bench_c3) run bench_c3 600 python bench.py --config c3 --steps 5 --warmup 2 --full ;;
+    bench_c4) run bench_c4 600 python bench.py --config c4 --steps 3 --warmup 1 --full ;;
+    bench_c5) run bench_c5 600 python bench.py --config c5 --steps 5 --warmup 2 --full ;;
+    bench_c5mixed) run bench_c5mixed 600 python bench.py --config c5mixed --steps 5 --warmup 2 --full ;;
+    bench_sst) run bench_sst 600 python bench.py --config sst --steps 20 --warmup 3 --full ;;
+    others) run bench_c1 300 python bench.py --config c1 --steps 50 --warmup 5 --full
+            run bench_c3 600 python bench.py --config c3 --steps 5 --warmup 2 --full
+            run bench_c4 600 python bench.py --config c4 --steps 3 --warmup 1 --full
+            run bench_c5 600 python bench.py --config c5 --steps 5 --warmup 2 --full
+            run bench_c5mixed 600 python bench.py --config c5mixed --steps 5 --warmup 2 --full
+            run bench_sst 600 python bench.py --config sst --steps 20 --warmup 3 --full ;;
     prof_c3) prof prof_c3 600 --config c3 --steps 3 --warmup 1 --no-cpu-baseline --no-host-inclusive ;;
     prof_c4) prof prof_c4 600 --config c4 --steps 2 --warmup 1 --no-cpu-baseline ;;
     prof_c5) prof prof_c5 600 --config c5 --steps 3 --warmup 1 --no-cpu-baseline --no-host-c5 ;;
@@ -108,7 +108,7 @@ for step in "$@"; do
                  done ;;
     abenv_c3_1) abenv abenvc3 300 1 --config c3 --steps 3 --warmup 1 ;;
     abenv_c4_1) abenv abenvc4 400 1 --config c4 --steps 3 --warmup 1 ;;
-    bench_c1_excl) PBF_SHARED_READERS=0 run bench_c1_excl 300 python bench.py --config c1 --steps 50 --warmup 5 ;;
+    bench_c1_excl) PBF_SHARED_READERS=0 run bench_c1_excl 300 python bench.py --config c1 --steps 50 --warmup 5 --full ;;
     prof_c4_serial) PBF_STREAMS=1 prof prof_c4_serial 600 --config c4 --steps 2 --warmup 1 --no-cpu-baseline ;;
     ab_c3) ab abc3 300 1 --config c3 --steps 3 --warmup 1 ;;
     ab_c3_2) ab abc3 300 2 --config c3 --steps 3 --warmup 1 ;;
@@ -118,11 +118,11 @@ for step in "$@"; do
     selflaunch) export PBF_BENCH_DEVICE=0 PBF_BENCH_BACKEND=gloo
                 run sl_c2_n2 300 python bench.py --gpus 2 --steps 10 --warmup 3 --no-host-inclusive
                 run sl_c2_n4 300 python bench.py --gpus 4 --steps 10 --warmup 3 --no-host-inclusive
-                run sl_c5_n2 300 python bench.py --gpus 2 --config c5 --steps 3 --warmup 1 --no-host-c5
+                run sl_c5_n2 300 python bench.py --gpus 2 --config c5 --steps 3 --warmup 1 --full --no-host-c5
                 unset PBF_BENCH_DEVICE PBF_BENCH_BACKEND ;;
     final_a) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
              run pytest 900 python -u -m pytest tests -m gpu -x -v -rf --timeout 150 --timeout-method thread
-             run bench 600 python bench.py
+             run bench 600 python bench.py --full
              prof prof 600 --steps 20 --warmup 5 --no-cpu-baseline --no-host-inclusive
              traffic c2 --steps 5 --warmup 2 ;;
     final_b) TRAFFIC_ARGS="--probe-scale 2.0" traffic c3 --config c3 --steps 2 --warmup 1
@@ -135,15 +135,15 @@ for step in "$@"; do
              TRAFFIC_ARGS="--probe-scale 3.0" traffic c5 --config c5 --steps 2 --warmup 1 --no-host-c5 --no-compare ;;
     final_1) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
              run pytest 900 python -u -m pytest tests -m gpu -x -v -rf --timeout 150 --timeout-method thread
-             run bench 600 python bench.py
+             run bench 600 python bench.py --full
              prof prof 600 --steps 20 --warmup 5 --no-cpu-baseline --no-host-inclusive
-             run bench_c1 300 python bench.py --config c1 --steps 50 --warmup 5
-             PBF_SHARED_READERS=0 run bench_c1_excl 300 python bench.py --config c1 --steps 50 --warmup 5 ;;
-    final_2) run bench_c3 600 python bench.py --config c3 --steps 5 --warmup 2
-             run bench_c4 600 python bench.py --config c4 --steps 3 --warmup 1
-             run bench_c5 600 python bench.py --config c5 --steps 5 --warmup 2
-             run bench_c5mixed 600 python bench.py --config c5mixed --steps 5 --warmup 2
-             run bench_sst 600 python bench.py --config sst --steps 20 --warmup 3
+             run bench_c1 300 python bench.py --config c1 --steps 50 --warmup 5 --full
+             PBF_SHARED_READERS=0 run bench_c1_excl 300 python bench.py --config c1 --steps 50 --warmup 5 --full ;;
+    final_2) run bench_c3 600 python bench.py --config c3 --steps 5 --warmup 2 --full
+             run bench_c4 600 python bench.py --config c4 --steps 3 --warmup 1 --full
+             run bench_c5 600 python bench.py --config c5 --steps 5 --warmup 2 --full
+             run bench_c5mixed 600 python bench.py --config c5mixed --steps 5 --warmup 2 --full
+             run bench_sst 600 python bench.py --config sst --steps 20 --warmup 3 --full
              prof prof_c3 600 --config c3 --steps 3 --warmup 1 --no-cpu-baseline --no-host-inclusive
              PBF_STREAMS=1 prof prof_c4_serial 600 --config c4 --steps 2 --warmup 1 --no-cpu-baseline
              prof prof_c5 600 --config c5 --steps 3 --warmup 1 --no-cpu-baseline --no-host-c5
@@ -151,13 +151,13 @@ for step in "$@"; do
              run sl_c2_n2 300 python bench.py --gpus 2 --steps 10 --warmup 3 --no-host-inclusive
              run sl_c2_n4 300 python bench.py --gpus 4 --steps 10 --warmup 3 --no-host-inclusive
              unset PBF_BENCH_DEVICE PBF_BENCH_BACKEND ;;
-    final_c) run bench_c1 300 python bench.py --config c1 --steps 50 --warmup 5
-             PBF_SHARED_READERS=0 run bench_c1_excl 300 python bench.py --config c1 --steps 50 --warmup 5
-             run bench_c3 600 python bench.py --config c3 --steps 5 --warmup 2
-             run bench_c4 600 python bench.py --config c4 --steps 3 --warmup 1
-             run bench_c5 600 python bench.py --config c5 --steps 5 --warmup 2
-             run bench_c5mixed 600 python bench.py --config c5mixed --steps 5 --warmup 2
-             run bench_sst 600 python bench.py --config sst --steps 20 --warmup 3 ;;
+    final_c) run bench_c1 300 python bench.py --config c1 --steps 50 --warmup 5 --full
+             PBF_SHARED_READERS=0 run bench_c1_excl 300 python bench.py --config c1 --steps 50 --warmup 5 --full
+             run bench_c3 600 python bench.py --config c3 --steps 5 --warmup 2 --full
+             run bench_c4 600 python bench.py --config c4 --steps 3 --warmup 1 --full
+             run bench_c5 600 python bench.py --config c5 --steps 5 --warmup 2 --full
+             run bench_c5mixed 600 python bench.py --config c5mixed --steps 5 --warmup 2 --full
+             run bench_sst 600 python bench.py --config sst --steps 20 --warmup 3 --full ;;
     final_d) prof prof_c3 600 --config c3 --steps 3 --warmup 1 --no-cpu-baseline --no-host-inclusive
              PBF_STREAMS=1 prof prof_c4_serial 600 --config c4 --steps 2 --warmup 1 --no-cpu-baseline
              prof prof_c5 600 --config c5 --steps 3 --warmup 1 --no-cpu-baseline --no-host-c5
@@ -167,7 +167,7 @@ for step in "$@"; do
              unset PBF_BENCH_DEVICE PBF_BENCH_BACKEND ;;
     final) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
            run pytest 900 python -u -m pytest tests -m gpu -x -v -rf --timeout 150 --timeout-method thread
-           run bench 600 python bench.py
+           run bench 600 python bench.py --full
            prof prof 600 --steps 20 --warmup 5 --no-cpu-baseline --no-host-inclusive
            traffic c2 --steps 5 --warmup 2 ;;
     pmc_c3_insts) for pc in "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS" \
@@ -178,7 +178,7 @@ for step in "$@"; do
     c5sim8) run c5sim_keys_w8 600 python bench.py --config c5 --sim-world 8 --sim-rank 0 --c5-layout keys --steps 10 --warmup 3 --no-host-c5 --no-cpu-baseline --no-compare
             prof prof_c5sim_keys_w8 600 --config c5 --sim-world 8 --sim-rank 0 --c5-layout keys --steps 10 --warmup 3 --no-host-c5 --no-cpu-baseline --no-compare ;;
     sl_c5) export PBF_BENCH_DEVICE=0 PBF_BENCH_BACKEND=gloo
-           run sl_c5_n2 300 python bench.py --gpus 2 --config c5 --steps 3 --warmup 1 --no-host-c5
+           run sl_c5_n2 300 python bench.py --gpus 2 --config c5 --steps 3 --warmup 1 --full --no-host-c5
            unset PBF_BENCH_DEVICE PBF_BENCH_BACKEND ;;
     diag_repl) run diag_repl 300 python tools/diag/replicate_check.py
                run diag_repl_pytest 300 python -u -m pytest tests/test_gpu_device_resident.py -m gpu -x -v -rf --timeout 150 --timeout-method thread -k "replicate" ;;
