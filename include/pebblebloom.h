@@ -323,6 +323,56 @@ int pbf_key_range_mask(int device, void* stream, const uint8_t* keys, const uint
                        uint64_t n, const uint8_t* bounds, const uint64_t* bound_offsets, uint32_t ntables, uint8_t* out,
                        int on_device);
 
+/* ---- Resident SSTables: the point lookup of SSTable.get (src/sstable.py:150-187) and of
+ * LsmStorage.get's walk (src/lsm_storage.py:164-179) for a batch of keys, over tables whose data
+ * sections stay in device memory until closed (no cache, no eviction). */
+typedef struct pbf_sstable pbf_sstable_t;
+
+/* Copies a data section (every DataBlock back to back, blocks.py:33-37; data_len bytes, host
+ * memory, or device memory on `device` with data_on_device = 1) to the device once and validates
+ * it there.  Block b is data[block_off[b], block_off[b+1]) -- the meta blocks' offsets plus
+ * meta_block_offset, nblocks+1 entries in HOST memory, from 0 to data_len.  Per block: count >= 1
+ * and 2*count+2 <= block bytes; offsets[0] == 0, strictly ascending, inside the record area; per
+ * record 8 + key_size + value_size == its extent with both sizes >= 0; keys strictly ascending in
+ * unsigned bytewise order, inside and across blocks.  Any violation: PBF_ERR_INVALID and a
+ * message that names the rule; nothing stays allocated.  A table that passed cannot make a lookup
+ * read outside its data section.  (The reference writes key_size in characters, record.py:25, and
+ * reads it as bytes, :77-79: it cannot read back a table that stores a non-ASCII key; such a
+ * table breaks the size rule and is refused.)  Synchronous. */
+int pbf_sst_open(int device, const uint8_t* data, uint64_t data_len, const uint32_t* block_off, uint32_t nblocks,
+                 int data_on_device, pbf_sstable_t** out);
+/* Waits for every lookup that holds the table (lookups hold its lock shared, close takes it
+ * exclusively; asynchronous lookups are waited for through their streams' events), then frees it.
+ * A handle that was closed is refused (PBF_ERR_INVALID) by every later call. */
+int pbf_sst_close(pbf_sstable_t* t);
+int pbf_sst_info(pbf_sstable_t* t, uint32_t* nblocks, uint64_t* nrecords, uint64_t* data_len);
+/* The validated block index, 4 words per block: offset of the first record, of the last record,
+ * of the u16 array, and the record count (offsets into the data section). */
+int pbf_sst_block_index(pbf_sstable_t* t, uint32_t* out, uint32_t nblocks);
+
+/* The get walk for n keys (layouts as pbf_probe: offsets != NULL, or fixed key_len) over
+ * `ntables` tables in row order: key i reads the tables whose mask has bit i set (masks[t]:
+ * ceil(n/8) bytes LSB-first, the hit-mask layout; masks == NULL or masks[t] == NULL: every key)
+ * and stops at the first that holds it.  table_out[i] = that row or -1; val_off_out[i] = the
+ * value's offset in that table's data section; val_len_out[i] = its length, -1 if absent (0 is a
+ * stored empty value, which the reference returns as b"").  ntables = 1 with no mask is
+ * SSTable.get.  `tables` and `masks` are host arrays; the tables share one device
+ * (PBF_ERR_INVALID otherwise).  on_device = 0: keys, masks and outputs are host memory,
+ * synchronous; on_device = 1: device pointers, asynchronous on `stream`. */
+int pbf_sst_get(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* keys, const uint64_t* offsets,
+                uint32_t key_len, uint64_t n, const uint8_t* const* masks, int on_device, void* stream,
+                int32_t* table_out, uint64_t* val_off_out, int32_t* val_len_out);
+
+/* Packs the values pbf_sst_get found: out_offsets[n+1] = the exclusive scan of max(val_len, 0)
+ * closed by the total, out_bytes[out_offsets[i], out_offsets[i+1]) = value i.  out_bytes == NULL:
+ * offsets only; otherwise it holds out_cap bytes (PBF_ERR_INVALID when the total is larger; an
+ * entry that names no table or lies outside its data section is refused the same way).
+ * on_device as for pbf_sst_get; with device pointers the work is ordered on `stream`, and the call
+ * returns once the total has been read back. */
+int pbf_sst_gather(pbf_sstable_t* const* tables, uint32_t ntables, const int32_t* table_idx, const uint64_t* val_off,
+                   const int32_t* val_len, uint64_t n, uint8_t* out_bytes, uint64_t out_cap, uint64_t* out_offsets,
+                   int on_device, void* stream);
+
 /* Synthetic keys straight into device memory (bench / tests; definitions in
  * pebbledb_amd/keys.py): 16 hex chars of splitmix64(seed + start + i), and the variable-length
  * 8..64-byte family (offsets must already hold the n+1 offsets, relative to offsets[0]).

@@ -5,5 +5,7 @@ hand-written HIP kernels for gfx950 in ``libpebblebloom.so`` (C-ABI: include/peb
 """
 from .bloom_filter import BloomFilter, may_contain_multi, may_contain_set, probe_multi_device, set_default_device
 from .keys import PackedKeys
+from .sstable_read import DeviceSSTable
 
-__all__ = ["BloomFilter", "PackedKeys", "may_contain_multi", "may_contain_set", "probe_multi_device", "set_default_device"]
+__all__ = ["BloomFilter", "DeviceSSTable", "PackedKeys", "may_contain_multi", "may_contain_set", "probe_multi_device",
+           "set_default_device"]

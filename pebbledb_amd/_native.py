@@ -81,6 +81,12 @@ SIGNATURES = {
                                    ctypes.POINTER(_u64)]),
     "pbf_plan_blocks": (_int, [_vp, _vp, _u64, _u64, _vp, _vp, ctypes.POINTER(_u64)]),
     "pbf_key_range_mask": (_int, [_int, _vp, _u8p, _vp, _u32, _u64, _u8p, _vp, _u32, _u8p, _int]),
+    "pbf_sst_open": (_int, [_int, _u8p, _u64, _vp, _u32, _int, ctypes.POINTER(_vp)]),
+    "pbf_sst_close": (_int, [_vp]),
+    "pbf_sst_info": (_int, [_vp, ctypes.POINTER(_u32), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "pbf_sst_block_index": (_int, [_vp, _vp, _u32]),
+    "pbf_sst_get": (_int, [_vp, _u32, _u8p, _vp, _u32, _u64, _vp, _int, _vp, _vp, _vp, _vp]),
+    "pbf_sst_gather": (_int, [_vp, _u32, _vp, _vp, _vp, _u64, _u8p, _u64, _vp, _int, _vp]),
     "pbf_gen_splitmix_hex": (_int, [_int, _vp, _u8p, _u64, _u64, _u64]),
     "pbf_gen_varlen": (_int, [_int, _vp, _u8p, _vp, _u64, _u64, _u64]),
     "pbf_last_error": (ctypes.c_char_p, []),

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <map>
 #include <mutex>
+#include <set>
 #include <shared_mutex>
 #include <atomic>
 #include <string>
@@ -33,6 +34,7 @@
 #include "lsm_kernels.hpp"
 #include "set_kernels.hpp"
 #include "reader_service.hpp"
+#include "sstable_read_kernels.hpp"
 
 using namespace pbf;
 
@@ -3575,6 +3577,389 @@ int pbf_gen_varlen(int device, void* stream, uint8_t* out_dev, const uint64_t* o
     k_gen_varlen<<<grid_for(n, 256), 256, 0, static_cast<hipStream_t>(stream)>>>(out_dev, offsets_dev, seed, start, n);
     CHECK_LAUNCH();
     if (!stream) HIP_TRY(hipStreamSynchronize(nullptr));  // as pbf_gen_splitmix_hex
+    return PBF_OK;
+}
+
+}  // extern "C"
+
+// ====================================================================== resident SSTables
+// The point lookup of SSTable.get / LsmStorage.get over tables held in HBM
+// (csrc/sstable_read_kernels.hpp).
+struct pbf_sstable {
+    int device = 0;
+    std::shared_mutex mu;  // lookups hold it shared, pbf_sst_close exclusively
+    DevBuf data, index, prefix;  // the data section (+16 bytes), SstBlock[nblocks], last-key prefixes
+    uint64_t data_len = 0, nrecords = 0;
+    uint32_t nblocks = 0;
+    std::mutex ev_mu;
+    std::map<hipStream_t, hipEvent_t> users;  // the last asynchronous lookup per caller stream
+};
+
+namespace {
+
+// Live handles: a lookup takes a handle's lock (shared) only while the handle is listed here,
+// under this mutex; pbf_sst_close unlists the handle first, then waits for the shared holders.
+std::shared_mutex g_sst_mu;
+std::set<pbf_sstable_t*> g_sst_live;
+
+struct SstCtx {
+    std::mutex mu;
+    hipStream_t stream = nullptr;
+    DevBuf keys, offs, masks, out, tmp, rep, gat;
+};
+
+SstCtx& sst_ctx(int device) {
+    static std::mutex mu;
+    static std::map<int, SstCtx*> ctx;
+    std::lock_guard<std::mutex> lock(mu);
+    auto& p = ctx[device];
+    if (!p) p = new SstCtx();
+    return *p;
+}
+
+int sst_ctx_stream(SstCtx& c, int device) {
+    if (!c.stream) {
+        HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
+        register_stream(device, c.stream);
+    }
+    return PBF_OK;
+}
+
+// The tables of one call, each locked shared (once, however often it is named).
+struct SstLocks {
+    std::vector<pbf_sstable_t*> held;
+    int take(pbf_sstable_t* const* ts, uint32_t nt) {
+        if (!ts || nt == 0) return fail(PBF_ERR_INVALID, "no tables");
+        std::vector<pbf_sstable_t*> u(ts, ts + nt);
+        std::sort(u.begin(), u.end());
+        u.erase(std::unique(u.begin(), u.end()), u.end());
+        std::shared_lock<std::shared_mutex> reg(g_sst_mu);
+        for (pbf_sstable_t* t : u)
+            if (!t || !g_sst_live.count(t)) return fail(PBF_ERR_INVALID, "null or closed SSTable handle");
+        for (pbf_sstable_t* t : u)
+            if (t->device != u[0]->device) return fail(PBF_ERR_INVALID, "all tables of one call must share a device");
+        for (pbf_sstable_t* t : u) {
+            t->mu.lock_shared();
+            held.push_back(t);
+        }
+        return PBF_OK;
+    }
+    // an asynchronous lookup on `s` reads the tables until an event recorded now completes
+    int used_on(hipStream_t s) {
+        for (pbf_sstable_t* t : held) {
+            std::lock_guard<std::mutex> lock(t->ev_mu);
+            hipEvent_t& ev = t->users[s];
+            if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(ev, s));
+        }
+        return PBF_OK;
+    }
+    ~SstLocks() {
+        for (pbf_sstable_t* t : held) t->mu.unlock_shared();
+    }
+};
+
+std::string sst_rule_names(unsigned int rules) {
+    std::string s;
+    auto add = [&](unsigned int r, const char* name) {
+        if (rules & r) s += (s.empty() ? "" : "; ") + std::string(name);
+    };
+    add(kSstRuleCount, "block count: need count >= 1 and 2*count+2 <= block bytes");
+    add(kSstRuleOffsets, "record offsets: need offsets[0] == 0, strictly ascending, inside the record area");
+    add(kSstRuleSizes, "record sizes: need 8 + key_size + value_size == the record's extent, sizes >= 0 "
+                       "(a non-ASCII key breaks this: key_size counts characters)");
+    add(kSstRuleOrder, "key order: need strictly ascending keys (unsigned bytewise)");
+    return s;
+}
+
+void sst_free(pbf_sstable_t* t) {
+    for (auto& kv : t->users) {
+        (void)hipEventSynchronize(kv.second);
+        (void)hipEventDestroy(kv.second);
+    }
+    t->users.clear();
+    t->data.release();
+    t->index.release();
+    t->prefix.release();
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbf_sst_open(int device, const uint8_t* data, uint64_t data_len, const uint32_t* block_off, uint32_t nblocks,
+                 int data_on_device, pbf_sstable_t** out) {
+    if (!out) return fail(PBF_ERR_INVALID, "null out pointer");
+    *out = nullptr;
+    if (!data || !block_off) return fail(PBF_ERR_INVALID, "null pointer");
+    if (nblocks == 0 || data_len == 0) return fail(PBF_ERR_INVALID, "an SSTable needs at least one data block");
+    if (data_len > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "data section over 2 GiB (the file's offsets are i32)");
+    if (block_off[0] != 0 || block_off[nblocks] != data_len)
+        return fail(PBF_ERR_INVALID, "block offsets must run from 0 to the data section's length");
+    for (uint32_t b = 0; b < nblocks; ++b)
+        if (block_off[b + 1] < block_off[b]) return fail(PBF_ERR_INVALID, "block offsets must ascend");
+    HIP_TRY(hipSetDevice(device));
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    int rc = sst_ctx_stream(c, device);
+    if (rc) return rc;
+    pbf_sstable_t* t = new pbf_sstable();
+    t->device = device;
+    t->data_len = data_len;
+    t->nblocks = nblocks;
+    auto bail = [&](int code) {
+        (void)hipStreamSynchronize(c.stream);
+        sst_free(t);
+        delete t;
+        return code;
+    };
+#define SST_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return bail(fail(PBF_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); \
+    } while (0)
+    SST_TRY(t->data.ensure(data_len + 16));
+    SST_TRY(t->index.ensure(size_t(nblocks) * sizeof(SstBlock)));
+    SST_TRY(t->prefix.ensure(size_t(nblocks) * 8));
+    SST_TRY(c.offs.ensure((size_t(nblocks) + 1) * 4));
+    SST_TRY(c.rep.ensure(sizeof(SstReport)));
+    hipStream_t s = c.stream;
+    // (a device data section may come from the null stream or another one: the caller has
+    // completed it, as for every synchronous call)
+    SST_TRY(hipMemcpyAsync(t->data.p, data, data_len, data_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    SST_TRY(hipMemsetAsync(static_cast<uint8_t*>(t->data.p) + data_len, 0, 16, s));
+    SST_TRY(hipMemcpyAsync(c.offs.p, block_off, (size_t(nblocks) + 1) * 4, hipMemcpyHostToDevice, s));
+    SST_TRY(hipMemsetAsync(c.rep.p, 0, sizeof(SstReport), s));
+    auto* d = static_cast<const uint8_t*>(t->data.p);
+    auto* idx = static_cast<SstBlock*>(t->index.p);
+    auto* rep = static_cast<SstReport*>(c.rep.p);
+    k_sst_validate<<<nblocks, 256, 0, s>>>(d, static_cast<const uint32_t*>(c.offs.p), nblocks, idx,
+                                           static_cast<uint64_t*>(t->prefix.p), rep);
+    SST_TRY(hipGetLastError());
+    SstReport r{};
+    SST_TRY(hipMemcpyAsync(&r, rep, sizeof r, hipMemcpyDeviceToHost, s));
+    SST_TRY(hipStreamSynchronize(s));
+    if (!r.rules && nblocks > 1) {  // the seams between blocks, on an index that is whole
+        k_sst_validate_seams<<<grid_for(nblocks - 1, 256, 1u << 23), 256, 0, s>>>(d, idx, nblocks, rep);
+        SST_TRY(hipGetLastError());
+        SST_TRY(hipMemcpyAsync(&r, rep, sizeof r, hipMemcpyDeviceToHost, s));
+        SST_TRY(hipStreamSynchronize(s));
+    }
+#undef SST_TRY
+    if (r.rules || r.bad_blocks || r.bad_records || r.order_violations)
+        return bail(fail(PBF_ERR_INVALID, "SSTable refused (" + std::to_string(r.bad_blocks) + " bad blocks, " +
+                                              std::to_string(r.bad_records) + " bad records, " +
+                                              std::to_string(r.order_violations) + " order violations): " +
+                                              sst_rule_names(r.rules)));
+    t->nrecords = r.records;
+    {
+        std::unique_lock<std::shared_mutex> reg(g_sst_mu);
+        g_sst_live.insert(t);
+    }
+    *out = t;
+    return PBF_OK;
+}
+
+int pbf_sst_close(pbf_sstable_t* t) {
+    if (!t) return PBF_OK;
+    {
+        std::unique_lock<std::shared_mutex> reg(g_sst_mu);
+        if (!g_sst_live.erase(t)) return fail(PBF_ERR_INVALID, "closed or unknown SSTable handle");
+    }
+    // no lookup can take the handle any more; the ones that hold it shared finish first
+    {
+        std::unique_lock<std::shared_mutex> lock(t->mu);
+        (void)hipSetDevice(t->device);
+        sst_free(t);
+    }
+    delete t;
+    return PBF_OK;
+}
+
+int pbf_sst_info(pbf_sstable_t* t, uint32_t* nblocks, uint64_t* nrecords, uint64_t* data_len) {
+    SstLocks locks;
+    int rc = locks.take(&t, 1);
+    if (rc) return rc;
+    if (nblocks) *nblocks = t->nblocks;
+    if (nrecords) *nrecords = t->nrecords;
+    if (data_len) *data_len = t->data_len;
+    return PBF_OK;
+}
+
+int pbf_sst_block_index(pbf_sstable_t* t, uint32_t* out, uint32_t nblocks) {
+    SstLocks locks;
+    int rc = locks.take(&t, 1);
+    if (rc) return rc;
+    if (!out || nblocks != t->nblocks) return fail(PBF_ERR_INVALID, "out must hold 4 * nblocks words");
+    HIP_TRY(hipSetDevice(t->device));
+    HIP_TRY(hipMemcpy(out, t->index.p, size_t(nblocks) * sizeof(SstBlock), hipMemcpyDeviceToHost));
+    return PBF_OK;
+}
+
+int pbf_sst_get(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* keys, const uint64_t* offsets,
+                uint32_t key_len, uint64_t n, const uint8_t* const* masks, int on_device, void* stream,
+                int32_t* table_out, uint64_t* val_off_out, int32_t* val_len_out) {
+    SstLocks locks;
+    int rc = locks.take(tables, ntables);
+    if (rc) return rc;
+    if (n == 0) return PBF_OK;
+    if (!table_out || !val_off_out || !val_len_out || (!keys && !offsets)) return fail(PBF_ERR_INVALID, "null pointer");
+    if (!offsets && key_len == 0) return fail(PBF_ERR_INVALID, "fixed-width keys need key_len > 0");
+    const int device = tables[0]->device;
+    HIP_TRY(hipSetDevice(device));
+    const uint64_t stride = (n + 7) / 8;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint8_t* dk = keys;
+    const uint64_t* dko = offsets;
+    std::vector<const uint8_t*> dm(ntables, nullptr);
+    if (masks)
+        for (uint32_t t = 0; t < ntables; ++t) dm[t] = masks[t];
+    int32_t *dt = table_out, *dvl = val_len_out;
+    uint64_t* dvo = val_off_out;
+    std::unique_lock<std::mutex> ctx_lock;
+    SstCtx* c = nullptr;
+    if (!on_device) {
+        if (offsets)
+            for (uint64_t i = 0; i < n; ++i)
+                if (offsets[i + 1] < offsets[i]) return fail(PBF_ERR_INVALID, "key offsets must ascend");
+        c = &sst_ctx(device);
+        ctx_lock = std::unique_lock<std::mutex>(c->mu);
+        rc = sst_ctx_stream(*c, device);
+        if (rc) return rc;
+        s = c->stream;
+        const uint64_t kb = offsets ? offsets[n] - offsets[0] : n * uint64_t(key_len);
+        uint32_t nm = 0;
+        for (uint32_t t = 0; t < ntables; ++t) nm += dm[t] != nullptr;
+        HIP_TRY(c->keys.ensure(kb + 16));
+        HIP_TRY(c->offs.ensure((n + 1) * 8));
+        HIP_TRY(c->masks.ensure(uint64_t(nm) * stride + 16));
+        HIP_TRY(c->out.ensure(n * 16 + 16));
+        if (kb) HIP_TRY(hipMemcpyAsync(c->keys.p, keys + (offsets ? offsets[0] : 0), kb, hipMemcpyHostToDevice, s));
+        if (offsets) HIP_TRY(hipMemcpyAsync(c->offs.p, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+        dk = static_cast<const uint8_t*>(c->keys.p);
+        dko = offsets ? static_cast<const uint64_t*>(c->offs.p) : nullptr;
+        uint32_t j = 0;
+        for (uint32_t t = 0; t < ntables; ++t)
+            if (dm[t]) {
+                uint8_t* p = static_cast<uint8_t*>(c->masks.p) + uint64_t(j++) * stride;
+                HIP_TRY(hipMemcpyAsync(p, dm[t], stride, hipMemcpyHostToDevice, s));
+                dm[t] = p;
+            }
+        dvo = static_cast<uint64_t*>(c->out.p);
+        dt = reinterpret_cast<int32_t*>(dvo + n);
+        dvl = dt + n;
+    }
+    const Batch b = make_batch(dk, dko, key_len, n);
+    const uint32_t grid = grid_for(n, 256, 1u << 20);
+    for (uint32_t t0 = 0; t0 < ntables; t0 += kSstTablesPerLaunch) {
+        SstSet set{};
+        set.t0 = t0;
+        set.nt = std::min(kSstTablesPerLaunch, ntables - t0);
+        set.first = t0 == 0;
+        for (uint32_t j = 0; j < set.nt; ++j) {
+            const pbf_sstable_t* t = tables[t0 + j];
+            set.data[j] = static_cast<const uint8_t*>(t->data.p);
+            set.index[j] = static_cast<const SstBlock*>(t->index.p);
+            set.last_prefix[j] = static_cast<const uint64_t*>(t->prefix.p);
+            set.mask[j] = dm[t0 + j];
+            set.nblocks[j] = t->nblocks;
+        }
+        if (b.km == kVar)
+            k_lsm_get<kVar><<<grid, 256, 0, s>>>(b.ks, n, set, dt, dvo, dvl);
+        else
+            k_lsm_get<kFixedN><<<grid, 256, 0, s>>>(b.ks, n, set, dt, dvo, dvl);
+        CHECK_LAUNCH();
+    }
+    if (on_device) return locks.used_on(s);
+    HIP_TRY(hipMemcpyAsync(val_off_out, dvo, n * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(table_out, dt, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(val_len_out, dvl, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return PBF_OK;
+}
+
+int pbf_sst_gather(pbf_sstable_t* const* tables, uint32_t ntables, const int32_t* table_idx, const uint64_t* val_off,
+                   const int32_t* val_len, uint64_t n, uint8_t* out_bytes, uint64_t out_cap, uint64_t* out_offsets,
+                   int on_device, void* stream) {
+    SstLocks locks;
+    int rc = locks.take(tables, ntables);
+    if (rc) return rc;
+    if (!out_offsets || (n && (!table_idx || !val_off || !val_len))) return fail(PBF_ERR_INVALID, "null pointer");
+    const int device = tables[0]->device;
+    HIP_TRY(hipSetDevice(device));
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    rc = sst_ctx_stream(c, device);
+    if (rc) return rc;
+    hipStream_t s = on_device ? static_cast<hipStream_t>(stream) : c.stream;
+    const int32_t *dt = table_idx, *dvl = val_len;
+    const uint64_t* dvo = val_off;
+    uint64_t* doffs = out_offsets;
+    if (!on_device) {
+        HIP_TRY(c.out.ensure(n * 16 + 16));
+        HIP_TRY(c.offs.ensure((n + 1) * 8));
+        auto* o = static_cast<uint64_t*>(c.out.p);
+        if (n) {
+            HIP_TRY(hipMemcpyAsync(o, val_off, n * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(o + n, table_idx, n * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(reinterpret_cast<int32_t*>(o + n) + n, val_len, n * 4, hipMemcpyHostToDevice, s));
+        }
+        dvo = o;
+        dt = reinterpret_cast<const int32_t*>(o + n);
+        dvl = dt + n;
+        doffs = static_cast<uint64_t*>(c.offs.p);
+    }
+    // value_offsets[n+1]: the exclusive scan of max(val_len, 0), closed by the total
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(doffs, 0, 8, s));
+    } else {
+        const uint64_t ntiles = (n + kScanTile - 1) / kScanTile;
+        if (ntiles > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "batch too large");
+        HIP_TRY(c.tmp.ensure(ntiles * 8));
+        auto* sums = static_cast<uint64_t*>(c.tmp.p);
+        k_len_tile_sums<<<uint32_t(ntiles), kScanThreads, 0, s>>>(dvl, n, sums);
+        CHECK_LAUNCH();
+        k_len_tile_scan<<<1, kScanThreads, 0, s>>>(sums, ntiles);
+        CHECK_LAUNCH();
+        k_len_offsets<<<uint32_t(ntiles), kScanThreads, 0, s>>>(dvl, n, sums, doffs);
+        CHECK_LAUNCH();
+    }
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, doffs + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!on_device) HIP_TRY(hipMemcpyAsync(out_offsets, doffs, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    unsigned int err = 0;
+    if (out_bytes && total) {
+        if (total > out_cap) {
+            HIP_TRY(hipStreamSynchronize(s));
+            return fail(PBF_ERR_INVALID, "the values need " + std::to_string(total) + " bytes, out_bytes holds " +
+                                             std::to_string(out_cap));
+        }
+        uint8_t* dout = out_bytes;
+        if (!on_device) {
+            HIP_TRY(c.gat.ensure(total + 16));
+            dout = static_cast<uint8_t*>(c.gat.p);
+        }
+        HIP_TRY(c.rep.ensure(sizeof(SstReport)));
+        HIP_TRY(hipMemsetAsync(c.rep.p, 0, 4, s));
+        const uint32_t grid = grid_for(n, 256 / kGatherLanes, 1u << 20);
+        for (uint32_t t0 = 0; t0 < ntables; t0 += kSstTablesPerLaunch) {
+            SstDataSet set{};
+            set.t0 = t0;
+            set.nt = std::min(kSstTablesPerLaunch, ntables - t0);
+            for (uint32_t j = 0; j < set.nt; ++j) {
+                set.data[j] = static_cast<const uint8_t*>(tables[t0 + j]->data.p);
+                set.data_len[j] = uint32_t(tables[t0 + j]->data_len);
+            }
+            k_gather_values<<<grid, 256, 0, s>>>(set, dt, dvo, dvl, n, doffs, dout, ntables,
+                                                 static_cast<unsigned int*>(c.rep.p));
+            CHECK_LAUNCH();
+        }
+        HIP_TRY(hipMemcpyAsync(&err, c.rep.p, 4, hipMemcpyDeviceToHost, s));
+        if (!on_device) HIP_TRY(hipMemcpyAsync(out_bytes, dout, total, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err) return fail(PBF_ERR_INVALID, std::to_string(err) + " entries name no table or lie outside its data section");
     return PBF_OK;
 }
 

@@ -31,7 +31,8 @@ import numpy as np
 
 from . import _native
 from . import bloom_filter as _bfm
-from .bloom_filter import BloomFilter, _default_device, may_contain_multi, may_contain_set_bits
+from .bloom_filter import (BloomFilter, _default_device, may_contain_multi, may_contain_set_bits,
+                           probe_multi_device)
 from .keys import PackedKeys
 
 
@@ -78,6 +79,7 @@ def candidate_masks(keys, level0: Sequence[BloomFilter], levels: Sequence[Sequen
     pk = _pack(keys)
     nb = (pk.n + 7) // 8
     flat = [t for lvl in levels for t in lvl]
+    level0 = [getattr(f, "bloom_filter", f) for f in level0]  # a DeviceSSTable stands for its filter
     out = np.zeros((len(level0) + len(flat), nb), dtype=np.uint8)
     if pk.n == 0:
         return out
@@ -141,3 +143,116 @@ def _set_bits(b: int) -> tuple:
         if len(_SET_BITS) < 1 << 16:
             _SET_BITS[b] = r
     return r
+
+
+# ---------------------------------------------------------------------------- get: keys in, values out
+def _walk_device(keys_ptr: int, offsets_ptr: int, key_len: int, n: int, level0, flat, device: int, timings=None):
+    """The whole batched get on device memory (torch tensors hold the buffers): the filter and
+    key-range stage in their device-pointer forms (``probe_multi_device``,
+    ``pbf_key_range_mask`` with on_device=1), so the candidate masks never leave the GPU, then
+    ``pbf_sst_get`` and ``pbf_sst_gather``, all ordered on torch's current stream.  Returns device
+    tensors (table int32[n], values uint8[total], value_offsets int64[n+1], val_len int32[n]).
+    `timings`: a dict that receives HIP-event times of the three stages in ms."""
+    import torch
+
+    from .sstable_read import _handles
+
+    tables = list(level0) + list(flat)
+    hs = _handles(tables)
+    n0, T, nb = len(level0), len(tables), (n + 7) // 8
+    dev = torch.device("cuda", device)
+    vp = ctypes.c_void_p
+    L = _native.lib()
+    with torch.cuda.device(dev):
+        cur = torch.cuda.current_stream(dev)
+        sp = cur.cuda_stream
+
+        def mark():
+            e = torch.cuda.Event(enable_timing=True)
+            e.record(cur)
+            return e
+
+        masks = torch.zeros((T, nb), dtype=torch.uint8, device=dev)
+        e0 = mark()
+        if level0:
+            f0 = [t.bloom_filter for t in level0]
+            f0[0].wait_stream(sp)
+            probe_multi_device(f0, keys_ptr, n, [masks[i].data_ptr() for i in range(n0)], key_len, offsets_ptr)
+            f0[0].signal_stream(sp)
+        if flat:
+            enc = [s.encode("utf-8") for t in flat for s in (t.first_key, t.last_key)]
+            boffs = np.zeros(len(enc) + 1, dtype=np.int64)
+            np.cumsum(np.fromiter(map(len, enc), dtype=np.int64, count=len(enc)), out=boffs[1:])
+            bbytes = torch.from_numpy(np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8).copy()).to(dev)
+            boffs_d = torch.from_numpy(boffs).to(dev)
+            rng = torch.empty((len(flat), nb), dtype=torch.uint8, device=dev)
+            rc = L.pbf_key_range_mask(device, vp(sp or None), vp(keys_ptr), vp(offsets_ptr or None), key_len, n,
+                                      vp(bbytes.data_ptr()), vp(boffs_d.data_ptr()), len(flat), vp(rng.data_ptr()), 1)
+            _native.check(rc, "pbf_key_range_mask")
+            fl = [t.bloom_filter for t in flat]
+            fl[0].wait_stream(sp)
+            probe_multi_device(fl, keys_ptr, n, [masks[n0 + j].data_ptr() for j in range(len(flat))], key_len,
+                               offsets_ptr)
+            fl[0].signal_stream(sp)
+            masks[n0:] &= rng  # lsm_storage.py:173-175: in range, then may_contain
+        e1 = mark()
+        table = torch.empty(n, dtype=torch.int32, device=dev)
+        val_off = torch.empty(n, dtype=torch.int64, device=dev)
+        val_len = torch.empty(n, dtype=torch.int32, device=dev)
+        mp = (vp * T)(*[masks[t].data_ptr() for t in range(T)])
+        rc = L.pbf_sst_get(hs, T, vp(keys_ptr), vp(offsets_ptr or None), key_len, n, mp, 1, vp(sp or None),
+                           vp(table.data_ptr()), vp(val_off.data_ptr()), vp(val_len.data_ptr()))
+        _native.check(rc, "pbf_sst_get")
+        e2 = mark()
+        total = int(val_len.clamp(min=0).sum(dtype=torch.int64).item())
+        offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        vals = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
+        e3 = mark()
+        rc = L.pbf_sst_gather(hs, T, vp(table.data_ptr()), vp(val_off.data_ptr()), vp(val_len.data_ptr()), n,
+                              vp(vals.data_ptr()) if total else None, total, vp(offs.data_ptr()), 1, vp(sp or None))
+        _native.check(rc, "pbf_sst_gather")
+        e4 = mark()
+        cur.synchronize()
+        if timings is not None:
+            timings.update(filter_ms=e0.elapsed_time(e1), walk_ms=e1.elapsed_time(e2), gather_ms=e3.elapsed_time(e4))
+    return table, vals[:total], offs, val_len
+
+
+def get_batch(keys, level0, levels):
+    """``LsmStorage.get`` with empty memtables for a batch of keys (lsm_storage.py:164-179), keys in,
+    values out: (table int32[n], values uint8[], value_offsets uint64[n+1]).  table[i] is the row
+    (``candidate_masks``' numbering: L0 newest first, then level by level) of the SSTable whose
+    value the reference returns for key i, -1 when it returns None; value i =
+    values[value_offsets[i]:value_offsets[i+1]] (empty when absent, and for a stored empty value,
+    which the reference returns as ``b""``).  `level0` and each level hold ``DeviceSSTable``s on
+    one device.  The keys go to the device once; the candidate masks are computed and consumed
+    there (``_walk_device``)."""
+    import torch
+
+    pk = _pack(keys)
+    level0 = list(level0)
+    flat = [t for lvl in levels for t in lvl]
+    tables = level0 + flat
+    n = pk.n
+    if n == 0 or not tables:
+        return np.full(n, -1, dtype=np.int32), np.zeros(0, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64)
+    devs = {t.device for t in tables}
+    if len(devs) > 1:
+        raise ValueError(f"all tables of one call must share a device, got devices {sorted(devs)}")
+    device = tables[0].device
+    dev = torch.device("cuda", device)
+    def upload(a):  # (torch wants a writable array: packed keys may view an immutable bytes object)
+        return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
+
+    kd = upload(pk.data if pk.data.size else np.zeros(1, np.uint8))
+    od = None if pk.offsets is None else upload(pk.offsets.view(np.int64))
+    table, vals, offs, _ = _walk_device(kd.data_ptr(), 0 if od is None else od.data_ptr(), pk.key_len, n, level0, flat,
+                                        device)
+    return table.cpu().numpy(), vals.cpu().numpy(), offs.cpu().numpy().view(np.uint64)
+
+
+def get_many(keys, level0, levels) -> list:
+    """[LsmStorage.get(key) for key in keys] with empty memtables: bytes, or None."""
+    table, vals, offs = get_batch(keys, level0, levels)
+    raw = vals.tobytes()
+    return [raw[int(offs[i]):int(offs[i + 1])] if table[i] >= 0 else None for i in range(len(table))]

@@ -60,7 +60,7 @@ for step in "$@"; do
     profq) prof profq 300 --steps 20 --warmup 5 --no-cpu-baseline --no-host-inclusive ;;
     traffic) traffic c2 --steps 5 --warmup 2 ;;
     traffic_c3) TRAFFIC_ARGS="--probe-scale 2.0" traffic c3 --config c3 --steps 2 --warmup 1 ;;  # two equal 100M-key pipelines per probe pass
-    traffic_c4) traffic c4 --config c4 --steps 2 --warmup 1 ;;  # per-filter build pass (bench scales by the rank's filters)
+    traffic_c4) traffic c4 --config c4 --steps 2 --warmup 1 --full ;;  # per-filter build pass (bench scales by the rank's filters)
     traffic_c5) TRAFFIC_ARGS="--probe-scale 1.0" traffic c5 --config c5 --steps 2 --warmup 1 --no-host-c5 --no-compare ;;  # one pipeline (the 100M-key batch)
     pmcall) run pmcall 2400 tools/pmc_passes.sh gpurun_out/pmcall ;;
     pmc_c3) run pmc_c3 2400 tools/pmc_passes.sh gpurun_out/pmc_c3 --config c3 ;;
@@ -126,12 +126,12 @@ for step in "$@"; do
              prof prof 600 --steps 20 --warmup 5 --no-cpu-baseline --no-host-inclusive
              traffic c2 --steps 5 --warmup 2 ;;
     final_b) TRAFFIC_ARGS="--probe-scale 2.0" traffic c3 --config c3 --steps 2 --warmup 1
-             traffic c4 --config c4 --steps 2 --warmup 1
+             traffic c4 --config c4 --steps 2 --warmup 1 --full
              TRAFFIC_ARGS="--probe-scale 3.0" traffic c5 --config c5 --steps 2 --warmup 1 --no-host-c5 --no-compare ;;
     traffic_c5b) TRAFFIC_ARGS="--probe-scale 3.0" traffic c5 --config c5 --steps 2 --warmup 1 --no-host-c5 --no-compare ;;
     traffic_all) traffic c2 --steps 5 --warmup 2
              TRAFFIC_ARGS="--probe-scale 2.0" traffic c3 --config c3 --steps 2 --warmup 1
-             traffic c4 --config c4 --steps 2 --warmup 1
+             traffic c4 --config c4 --steps 2 --warmup 1 --full
              TRAFFIC_ARGS="--probe-scale 3.0" traffic c5 --config c5 --steps 2 --warmup 1 --no-host-c5 --no-compare ;;
     final_1) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
              run pytest 900 python -u -m pytest tests -m gpu -x -v -rf --timeout 150 --timeout-method thread
