@@ -258,7 +258,19 @@ int pbf_scratch_bytes(int device, uint64_t* out);
  * and is written at byte block_out[b] of out (block_out[nblocks] = section size); a block's
  * records may total at most 65536 bytes.  One workgroup per block assembles it in LDS.
  * on_device = 0: all pointers are host memory (checked, staged, section copied back);
- * on_device = 1: device pointers, the offsets start at the data pointers. Synchronous. */
+ * on_device = 1: every pointer is device memory and nothing is checked on the host (n is not
+ * used): the plan must be monotonic and in range; a block whose records exceed 65536 bytes is
+ * left unwritten and the call returns PBF_ERR_INVALID ("N block(s) exceed ..."), the other
+ * blocks are written.  keys, values and out may have any byte alignment (a slice of a larger
+ * allocation).  Offsets index from the keys / values pointers as passed: byte j of key i is
+ * keys[key_offsets[i] + j]; the first offset a block uses need not be 0 (key_offsets + r0,
+ * value_offsets + r0 with block_first relative to r0 encode a window of a run), and block_out
+ * need not be contiguous.  The kernel reads a span in whole 16-byte chunks aligned by ADDRESS:
+ * for a non-empty span [p, q) it may read any byte of [p & ~15, (q + 15) & ~15) — up to 15
+ * bytes before the first and after the last byte, never beyond the 16-byte line (hence the
+ * page) that holds a byte of the span; an empty span is not read.  It writes exactly the
+ * bytes [out + block_out[b], + the block's encoded size) of each block.  The kernel runs on the
+ * NULL stream and the call returns after it has finished.  Synchronous. */
 int pbf_encode_data_blocks(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
                            const uint64_t* value_offsets, uint64_t n, const uint64_t* block_first,
                            const uint64_t* block_out, uint64_t nblocks, uint8_t* out, int on_device);

@@ -3085,7 +3085,6 @@ int pbf_encode_data_blocks(int device, const uint8_t* keys, const uint64_t* key_
         register_stream(device, c.stream);
     }
     HIP_TRY(c.err.ensure(4));
-    HIP_TRY(hipMemsetAsync(c.err.p, 0, 4, c.stream));
     const uint8_t *dk = keys, *dv = values;
     const uint64_t *dko = key_offsets, *dvo = value_offsets, *dbf = block_first, *dbo = block_out;
     uint8_t* dout = out;
@@ -3096,7 +3095,7 @@ int pbf_encode_data_blocks(int device, const uint8_t* keys, const uint64_t* key_
             return fail(PBF_ERR_INVALID, "block plan must cover records [0, n) from byte 0");
         for (uint64_t b = 0; b < nblocks; ++b) {
             const uint64_t r0 = block_first[b], r1 = block_first[b + 1];
-            if (r1 < r0) return fail(PBF_ERR_INVALID, "block plan not monotonic");
+            if (r1 < r0 || r1 > n) return fail(PBF_ERR_INVALID, "block plan not monotonic");  // (> n: before offsets[r1] is read)
             const uint64_t dl = (key_offsets[r1] - key_offsets[r0]) + (value_offsets[r1] - value_offsets[r0]) + 8 * (r1 - r0);
             if (dl > kMaxBlockData) return fail(PBF_ERR_INVALID, "a block's records exceed 65536 bytes");
             if (block_out[b + 1] - block_out[b] != dl + 2 * (r1 - r0) + 2)
@@ -3124,8 +3123,10 @@ int pbf_encode_data_blocks(int device, const uint8_t* keys, const uint64_t* key_
         dbo = o + 2 * (n + 1) + nblocks + 1;
         dout = static_cast<uint8_t*>(c.out.p);
     }
+    // the error counter is zeroed once, on the stream the kernel runs on (device pointers: the
+    // NULL stream, which c.stream, a non-blocking one, is not ordered with)
     hipStream_t s = on_device ? nullptr : c.stream;
-    if (on_device) HIP_TRY(hipMemsetAsync(c.err.p, 0, 4, s));
+    HIP_TRY(hipMemsetAsync(c.err.p, 0, 4, s));
     k_encode_blocks<<<uint32_t(nblocks), 512, kEncodeLds, s>>>(dk, dko, dv, dvo, dbf, dbo, dout,
                                                                static_cast<unsigned int*>(c.err.p));
     CHECK_LAUNCH();
@@ -3152,7 +3153,7 @@ int pbf_build_sstable(pbf_filter_t* f, const uint8_t* keys, const uint64_t* key_
         return fail(PBF_ERR_INVALID, "block plan must cover records [0, n) from byte 0");
     for (uint64_t b = 0; b < nblocks; ++b) {
         const uint64_t r0 = block_first[b], r1 = block_first[b + 1];
-        if (r1 < r0) return fail(PBF_ERR_INVALID, "block plan not monotonic");
+        if (r1 < r0 || r1 > n) return fail(PBF_ERR_INVALID, "block plan not monotonic");  // (> n: before offsets[r1] is read)
         const uint64_t dl = (key_offsets[r1] - key_offsets[r0]) + (value_offsets[r1] - value_offsets[r0]) + 8 * (r1 - r0);
         if (dl > kMaxBlockData) return fail(PBF_ERR_INVALID, "a block's records exceed 65536 bytes");
         if (block_out[b + 1] - block_out[b] != dl + 2 * (r1 - r0) + 2)
@@ -3253,7 +3254,7 @@ int pbf_build_sstables(pbf_filter_t* const* filters, uint32_t ntables, const uin
         if (table_blocks[t + 1] <= table_blocks[t]) return fail(PBF_ERR_INVALID, "a table without blocks");
     for (uint64_t b = 0; b < nblocks; ++b) {
         const uint64_t r0 = block_first[b], r1 = block_first[b + 1];
-        if (r1 <= r0) return fail(PBF_ERR_INVALID, "block plan not increasing");
+        if (r1 <= r0 || r1 > n) return fail(PBF_ERR_INVALID, "block plan not increasing");  // (> n: before offsets[r1] is read)
         const uint64_t dl = (key_offsets[r1] - key_offsets[r0]) + (value_offsets[r1] - value_offsets[r0]) + 8 * (r1 - r0);
         if (dl > kMaxBlockData) return fail(PBF_ERR_INVALID, "a block's records exceed 65536 bytes");
         if (block_out[b + 1] - block_out[b] != dl + 2 * (r1 - r0) + 2)

@@ -24,20 +24,23 @@ __device__ __forceinline__ void lds_put_u32(uint8_t* p, uint32_t v) {
     p[3] = uint8_t(v >> 24);
 }
 
-// Bytes [s, e) of src into dst (LDS), read as aligned 16-byte chunks; returns the number of
-// UTF-8 characters (bytes that are not 10xxxxxx continuation bytes) when `count`.
+// Bytes [s, e) of src into dst (LDS), read as 16-byte chunks aligned by ADDRESS (src itself may
+// have any alignment, e.g. a slice of a tensor): every chunk holds >= 1 byte of the span, so a
+// read never leaves the 16-byte lines (hence the pages) the span lies on.  Returns the number
+// of UTF-8 characters (bytes that are not 10xxxxxx continuation bytes) when `count`.
 __device__ __forceinline__ uint32_t copy_span(const uint8_t* __restrict__ src, uint64_t s, uint64_t e, uint8_t* dst,
                                               bool count) {
     uint32_t chars = 0;
-    for (uint64_t a = s & ~uint64_t(15); a < e; a += 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(src + a);
+    const uint64_t lo = reinterpret_cast<uintptr_t>(src) + s, hi = reinterpret_cast<uintptr_t>(src) + e;
+    for (uint64_t a = lo & ~uint64_t(15); a < hi; a += 16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(a);
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const uint64_t pos = a + j;
-            if (pos >= s && pos < e) {
+            if (pos >= lo && pos < hi) {
                 const uint32_t c = (w[j >> 2] >> (8 * (j & 3))) & 0xFFu;
-                dst[pos - s] = uint8_t(c);
+                dst[pos - lo] = uint8_t(c);
                 if (count) chars += (c & 0xC0u) != 0x80u;
             }
         }
