@@ -11,8 +11,11 @@
  *   - All functions return 0 (PBF_OK) or a negative PBF_ERR_*; pbf_last_error() gives the
  *     message of the last failure on the calling thread.
  *   - Keys are UTF-8 bytes (bloom_filter.py:43).  A batch is either fixed-width (key i =
- *     keys[i*key_len, (i+1)*key_len)) or variable-length (key i = keys[offsets[i] - offsets[0],
- *     offsets[i+1] - offsets[0]); offsets has n+1 entries).
+ *     keys[i*key_len, (i+1)*key_len)) or variable-length (offsets has n+1 entries, key i is
+ *     offsets[i+1] - offsets[i] bytes).  offsets[0] may be non-zero (a window of a larger
+ *     batch): with host pointers `keys` is the buffer the offsets index (key i =
+ *     keys[offsets[i], offsets[i+1])); with device pointers `keys` is the window's first byte
+ *     (key i = keys[offsets[i] - offsets[0], offsets[i+1] - offsets[0])).
  *   - keys_on_device = 0: keys/offsets/hitmask are host pointers; the call copies what it needs
  *     (pinned staging + hipMemcpyAsync) and returns when the host buffers may be reused.
  *     keys_on_device = 1: they are device pointers on the filter's device; the call is
@@ -326,9 +329,14 @@ int pbf_plan_compaction(const uint64_t* key_offsets, const uint64_t* value_offse
 /* The level key-range pre-check of LsmStorage.get (src/lsm_storage.py:171-175) for a batch:
  * out[t * ceil(n/8) + i/8] bit (i & 7) = (first_t <= key_i <= last_t), Python str order =
  * bytewise lexicographic order of the UTF-8 keys.  Bounds are 2*ntables byte strings
- * (first_0, last_0, first_1, last_1, ...): bound j = bounds[bound_offsets[j] - bound_offsets[0],
- * bound_offsets[j+1] - bound_offsets[0]).  Keys as in pbf_probe (offsets != NULL) or fixed
- * key_len (offsets == NULL).  The mask layout is the hit-mask layout, so it ANDs directly with
+ * (first_0, last_0, first_1, last_1, ...) of at most 65536 bytes each, bound j being
+ * bound_offsets[j+1] - bound_offsets[j] bytes.  bound_offsets[0] may be non-zero, as offsets[0]
+ * may (a window): with host pointers `bounds` and `keys` are the buffers the offsets index
+ * (bound j = bounds[bound_offsets[j], bound_offsets[j+1])), with device pointers they are the
+ * windows' first bytes (bound j = bounds[bound_offsets[j] - bound_offsets[0], bound_offsets[j+1] -
+ * bound_offsets[0])).  Keys as in pbf_probe (offsets != NULL) or fixed key_len (offsets ==
+ * NULL).  Every byte of the T rows is written (the pad bits of a row's last byte as zeros) and
+ * nothing outside them.  The mask layout is the hit-mask layout, so it ANDs directly with
  * the table's filter hit mask.  on_device = 0: host pointers, synchronous; on_device = 1:
  * device pointers (bound_offsets is read back first), asynchronous on `stream`. */
 int pbf_key_range_mask(int device, void* stream, const uint8_t* keys, const uint64_t* offsets, uint32_t key_len,

@@ -84,16 +84,29 @@ def candidate_masks(keys, level0: Sequence[BloomFilter], levels: Sequence[Sequen
     if pk.n == 0:
         return out
     if level0:
-        out[:len(level0)] = may_contain_multi(level0, pk)
+        out[:len(level0)] = _probe_rows(level0, pk)
     if flat:
         rng = key_range_masks(pk, [(t.first_key, t.last_key) for t in flat],
                               device=flat[0].bloom_filter.device)
         live = [j for j in range(len(flat)) if rng[j].any()]  # tables no key of the batch reaches
         if live:
-            hits = may_contain_multi([flat[j].bloom_filter for j in live], pk)
+            hits = _probe_rows([flat[j].bloom_filter for j in live], pk)
             for r, j in enumerate(live):
                 out[len(level0) + j] = rng[j] & hits[r]
     return out
+
+
+def _probe_rows(filters, pk: PackedKeys) -> np.ndarray:
+    """``may_contain_multi`` row per entry of `filters`; a filter object that stands behind
+    several tables (``pbf_probe_multi`` takes each filter once) is probed once and its row shared."""
+    first = {}
+    slot = [first.setdefault(id(f), len(first)) for f in filters]
+    if len(first) == len(filters):
+        return may_contain_multi(filters, pk)
+    distinct = [None] * len(first)
+    for f, s in zip(filters, slot):
+        distinct[s] = f
+    return may_contain_multi(distinct, pk)[slot]
 
 
 def candidate_lists(masks: np.ndarray, n: int) -> list[list[int]]:
@@ -114,6 +127,10 @@ def candidates_one(key: str, level0: Sequence[BloomFilter], levels: Sequence[Seq
     if r is not None:
         return r
     n0 = len(level0)
+    if n0 and not isinstance(key, str):
+        # the reference probes L0 before any level's range check (:164-165): its bloom check's
+        # AttributeError (key.encode) comes before the TypeError of `str <= key` (:173)
+        may_contain_set_bits(list(level0), key)
     in_range, tested = [], list(level0)
     j = n0
     for lvl in levels:
