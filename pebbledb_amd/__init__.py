@@ -4,8 +4,9 @@ Drop-in for MaudGautier/pebbledb ``src/bloom_filter.py`` (``BloomFilter``), back
 hand-written HIP kernels for gfx950 in ``libpebblebloom.so`` (C-ABI: include/pebblebloom.h).
 """
 from .bloom_filter import BloomFilter, may_contain_multi, may_contain_set, probe_multi_device, set_default_device
+from .compaction import compact_l0, compact_level, concat_tables, merge_tables
 from .keys import PackedKeys
 from .sstable_read import DeviceSSTable
 
-__all__ = ["BloomFilter", "DeviceSSTable", "PackedKeys", "may_contain_multi", "may_contain_set", "probe_multi_device",
-           "set_default_device"]
+__all__ = ["BloomFilter", "DeviceSSTable", "PackedKeys", "compact_l0", "compact_level", "concat_tables",
+           "may_contain_multi", "may_contain_set", "merge_tables", "probe_multi_device", "set_default_device"]

@@ -23,6 +23,7 @@ PBF_DETAIL_RING, PBF_DETAIL_SORT, PBF_DETAIL_ONE_KEY, PBF_DETAIL_SET, PBF_DETAIL
 PBF_DETAIL_SHARED = 32
 PBF_DETAIL_RESIDENT = 64
 PBF_COPY_BOUNCE = 1
+PBF_MERGE_DEDUP, PBF_MERGE_CONCAT = 0, 1
 
 _u8p = ctypes.c_void_p
 _vp = ctypes.c_void_p
@@ -87,6 +88,8 @@ SIGNATURES = {
     "pbf_sst_block_index": (_int, [_vp, _vp, _u32]),
     "pbf_sst_get": (_int, [_vp, _u32, _u8p, _vp, _u32, _u64, _vp, _int, _vp, _vp, _vp, _vp]),
     "pbf_sst_gather": (_int, [_vp, _u32, _vp, _vp, _vp, _u64, _u8p, _u64, _vp, _int, _vp]),
+    "pbf_sst_merge": (_int, [_vp, _u32, _int, _u8p, _u64, _vp, _u8p, _u64, _vp, _u64, ctypes.POINTER(_u64),
+                             ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _vp]),
     "pbf_gen_splitmix_hex": (_int, [_int, _vp, _u8p, _u64, _u64, _u64]),
     "pbf_gen_varlen": (_int, [_int, _vp, _u8p, _vp, _u64, _u64, _u64]),
     "pbf_last_error": (ctypes.c_char_p, []),

@@ -1,0 +1,107 @@
+"""Compaction over SSTables resident on the device: the record run that
+``force_compaction_l0`` / ``force_compaction_l1_or_more_level`` (reference
+src/lsm_storage.py:253-294) feed to ``_compact``, produced from ``DeviceSSTable``s without the
+reference's iterators, and the output SSTable files built from it.
+
+``merge_tables`` is ``MergingIterator([SSTableIterator(t) for t in tables])``
+(src/iterators.py:110-190): every distinct key in ascending order, each with the record of the
+lowest table index that stores it (``tables[0]`` is the first iterator; the heap key is
+``(key, iterator_index)`` and ``_filter_duplicate_keys`` keeps the first record of a key).  An
+empty value is a value like any other: the reference has no tombstones.  ``concat_tables`` is
+``ConcatenatingIterator`` (iterators.py:193-207): every record, table after table in list order.
+Both are one ``pbf_sst_merge`` call (csrc/sstable_merge_kernels.hpp): a merge by rank — every
+input record finds its place with one lower-bound search per other table — then scans over the
+ranked records and one packed copy of the kept keys and values.
+
+Keys order as unsigned bytes, which is the reference's ``str`` order for the keys a resident
+table can hold (``DeviceSSTable`` refuses the non-ASCII keys the reference cannot read back).
+
+``compact_l0`` / ``compact_level`` are the merge / concatenation followed by
+``sstable_data.build_sstables``: the files ``_compact`` writes, without the state update and the
+manifest event, which stay with the caller.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Sequence
+
+import numpy as np
+
+from . import _native
+from .keys import PackedKeys, PackedRecords
+from .sstable_data import BLOCK_SIZE, build_sstables
+from .sstable_read import _handles
+
+_vp = ctypes.c_void_p
+MAX_TABLES = 64  # kSstTablesPerLaunch: the tables travel in one kernel's arguments
+
+
+def _bounds(tables) -> tuple[int, int]:
+    """(records, key + value bytes) of the tables together, from host-known sizes: a data section
+    is its records (8 bytes of sizes each, then key and value), one u16 per record and one u16
+    per block."""
+    n = nbytes = 0
+    nb, nr, dl = ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint64()
+    for t in tables:
+        _native.check(_native.lib().pbf_sst_info(t._h, ctypes.byref(nb), ctypes.byref(nr), ctypes.byref(dl)),
+                      "pbf_sst_info")
+        n += nr.value
+        nbytes += dl.value - 10 * nr.value - 2 * nb.value
+    return n, nbytes
+
+
+def _run(tables: Sequence, mode: int) -> PackedRecords:
+    tables = list(tables)
+    if not tables:
+        raise ValueError("no tables to merge")
+    if len(tables) > MAX_TABLES:
+        raise ValueError(f"a merge takes at most {MAX_TABLES} tables, got {len(tables)}")
+    hs = _handles(tables)
+    n, nbytes = _bounds(tables)
+    keys = np.empty(nbytes, dtype=np.uint8)
+    values = np.empty(nbytes, dtype=np.uint8)
+    ko = np.empty(n + 1, dtype=np.uint64)
+    vo = np.empty(n + 1, dtype=np.uint64)
+    n_out, kb, vb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    rc = _native.lib().pbf_sst_merge(hs, len(tables), mode, _vp(keys.ctypes.data) if nbytes else None, nbytes,
+                                     _vp(ko.ctypes.data), _vp(values.ctypes.data) if nbytes else None, nbytes,
+                                     _vp(vo.ctypes.data), n + 1, ctypes.byref(n_out), ctypes.byref(kb),
+                                     ctypes.byref(vb), 0, None)
+    _native.check(rc, "pbf_sst_merge")
+    m = n_out.value
+    pk = PackedKeys(keys[:kb.value], m, offsets=ko[:m + 1])
+    return PackedRecords(pk, values[:vb.value], vo[:m + 1])
+
+
+def merge_tables(tables: Sequence) -> PackedRecords:
+    """``MergingIterator`` over the tables' ``SSTableIterator``s as a packed run (see the module
+    docstring).  At most 64 tables, all open, distinct and on one device (ValueError otherwise)."""
+    return _run(tables, _native.PBF_MERGE_DEDUP)
+
+
+def concat_tables(tables: Sequence) -> PackedRecords:
+    """``ConcatenatingIterator`` over the tables' ``SSTableIterator``s as a packed run: every
+    record in list order, also where the tables overlap or are out of order."""
+    return _run(tables, _native.PBF_MERGE_CONCAT)
+
+
+def compact_l0(tables: Sequence, max_sstable_size: int = 262_144_000, block_size: int = BLOCK_SIZE,
+               fp_rate: float = 0.001, device=None):
+    """``force_compaction_l0`` (lsm_storage.py:253-260) up to the files: ``merge_tables`` then
+    ``build_sstables``; returns what ``build_sstables`` returns, (outputs, records written).
+
+    The merged run makes one host round trip between the two calls: ``merge_tables`` brings it to
+    host memory and ``build_sstables`` uploads it again (``pbf_build_sstables`` reads host
+    memory)."""
+    tables = list(tables)
+    run = merge_tables(tables)
+    return build_sstables(run, None, max_sstable_size, block_size, fp_rate, tables[0].device if device is None else device)
+
+
+def compact_level(tables: Sequence, max_sstable_size: int = 262_144_000, block_size: int = BLOCK_SIZE,
+                  fp_rate: float = 0.001, device=None):
+    """``force_compaction_l1_or_more_level`` (lsm_storage.py:272-284) up to the files:
+    ``concat_tables`` then ``build_sstables``, with the same host round trip as ``compact_l0``."""
+    tables = list(tables)
+    run = concat_tables(tables)
+    return build_sstables(run, None, max_sstable_size, block_size, fp_rate, tables[0].device if device is None else device)

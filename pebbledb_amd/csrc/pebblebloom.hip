@@ -35,6 +35,7 @@
 #include "set_kernels.hpp"
 #include "reader_service.hpp"
 #include "sstable_read_kernels.hpp"
+#include "sstable_merge_kernels.hpp"
 
 using namespace pbf;
 
@@ -3594,6 +3595,9 @@ struct pbf_sstable {
     uint32_t nblocks = 0;
     std::mutex ev_mu;
     std::map<hipStream_t, hipEvent_t> users;  // the last asynchronous lookup per caller stream
+    std::mutex rb_mu;
+    DevBuf rec_base;  // uint32[nblocks+1], the records before each block: built by the first merge
+    bool rb_ready = false;
 };
 
 namespace {
@@ -3607,6 +3611,10 @@ struct SstCtx {
     std::mutex mu;
     hipStream_t stream = nullptr;
     DevBuf keys, offs, masks, out, tmp, rep, gat;
+    // pbf_sst_merge's working memory and (host form) output staging; merge_done = its last
+    // asynchronous call, which the next one waits for before it reuses them
+    DevBuf mslots, mpos, msums, mkeys, mvals, mko, mvo;
+    hipEvent_t merge_done = nullptr;
 };
 
 SstCtx& sst_ctx(int device) {
@@ -3682,6 +3690,7 @@ void sst_free(pbf_sstable_t* t) {
     t->data.release();
     t->index.release();
     t->prefix.release();
+    t->rec_base.release();
 }
 
 }  // namespace
@@ -3961,6 +3970,140 @@ int pbf_sst_gather(pbf_sstable_t* const* tables, uint32_t ntables, const int32_t
     }
     HIP_TRY(hipStreamSynchronize(s));
     if (err) return fail(PBF_ERR_INVALID, std::to_string(err) + " entries name no table or lie outside its data section");
+    return PBF_OK;
+}
+
+}  // extern "C"
+
+// ====================================================================== compaction merge
+// MergingIterator / ConcatenatingIterator over resident tables (csrc/sstable_merge_kernels.hpp).
+namespace {
+
+// rec_base[b] = the records of blocks [0, b), from the validated index: built once per handle.
+int sst_rec_base(pbf_sstable_t* t) {
+    std::lock_guard<std::mutex> lock(t->rb_mu);
+    if (t->rb_ready) return PBF_OK;
+    std::vector<SstBlock> idx(t->nblocks);
+    HIP_TRY(hipMemcpy(idx.data(), t->index.p, size_t(t->nblocks) * sizeof(SstBlock), hipMemcpyDeviceToHost));
+    std::vector<uint32_t> base(size_t(t->nblocks) + 1, 0);
+    uint64_t sum = 0;
+    for (uint32_t b = 0; b < t->nblocks; ++b) {
+        sum += idx[b].count;
+        if (idx[b].count == 0 || sum > 0xFFFFFFFFull) return fail(PBF_ERR_INVALID, "the SSTable's block index is not whole");
+        base[b + 1] = uint32_t(sum);
+    }
+    if (sum != t->nrecords) return fail(PBF_ERR_INVALID, "the SSTable's block index does not add up to its records");
+    HIP_TRY(t->rec_base.ensure(base.size() * 4));
+    HIP_TRY(hipMemcpy(t->rec_base.p, base.data(), base.size() * 4, hipMemcpyHostToDevice));
+    t->rb_ready = true;
+    return PBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint8_t* keys_out, uint64_t keys_cap,
+                  uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
+                  uint64_t offsets_cap, uint64_t* n_out, uint64_t* key_bytes_out, uint64_t* value_bytes_out,
+                  int on_device, void* stream) {
+    if (!tables || ntables == 0) return fail(PBF_ERR_INVALID, "no tables");
+    if (ntables > kSstTablesPerLaunch)
+        return fail(PBF_ERR_INVALID, "a merge takes at most " + std::to_string(kSstTablesPerLaunch) + " tables, got " +
+                                         std::to_string(ntables));
+    if (mode != PBF_MERGE_DEDUP && mode != PBF_MERGE_CONCAT) return fail(PBF_ERR_INVALID, "unknown merge mode");
+    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out)
+        return fail(PBF_ERR_INVALID, "null pointer");
+    {
+        std::vector<pbf_sstable_t*> u(tables, tables + ntables);
+        std::sort(u.begin(), u.end());
+        if (std::adjacent_find(u.begin(), u.end()) != u.end())
+            return fail(PBF_ERR_INVALID, "the same table is listed twice");
+    }
+    SstLocks locks;
+    int rc = locks.take(tables, ntables);
+    if (rc) return rc;
+    const int device = tables[0]->device;
+    HIP_TRY(hipSetDevice(device));
+    MergeSet set{};
+    set.nt = ntables;
+    uint64_t n = 0;
+    for (uint32_t t = 0; t < ntables; ++t) {
+        pbf_sstable_t* tb = tables[t];
+        if ((rc = sst_rec_base(tb))) return rc;
+        set.data[t] = static_cast<const uint8_t*>(tb->data.p);
+        set.index[t] = static_cast<const SstBlock*>(tb->index.p);
+        set.last_prefix[t] = static_cast<const uint64_t*>(tb->prefix.p);
+        set.rec_base[t] = static_cast<const uint32_t*>(tb->rec_base.p);
+        set.nblocks[t] = tb->nblocks;
+        set.in_base[t] = n;
+        n += tb->nrecords;
+    }
+    const uint64_t ntiles = (n + kScanTile - 1) / kScanTile;
+    if (n == 0 || ntiles > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "run too large");
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    rc = sst_ctx_stream(c, device);
+    if (rc) return rc;
+    if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
+    hipStream_t s = on_device ? static_cast<hipStream_t>(stream) : c.stream;
+    HIP_TRY(c.mslots.ensure(n * sizeof(MergeSlot)));
+    HIP_TRY(c.mpos.ensure(n * 8));
+    HIP_TRY(c.msums.ensure((kMergeTotals * ntiles + kMergeTotals) * 8));
+    auto* slots = static_cast<MergeSlot*>(c.mslots.p);
+    auto* pos = static_cast<uint64_t*>(c.mpos.p);
+    auto* sums = static_cast<uint64_t*>(c.msums.p);
+    uint64_t* totals = sums + kMergeTotals * ntiles;
+    // (a slot no record claims stays dropped: the ranks are a permutation, this is the belt)
+    HIP_TRY(hipMemsetAsync(slots, 0, n * sizeof(MergeSlot), s));
+    k_merge_rank<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(set, n, mode == PBF_MERGE_DEDUP, slots);
+    CHECK_LAUNCH();
+    k_merge_tile_sums<<<uint32_t(ntiles), kScanThreads, 0, s>>>(slots, n, sums, ntiles);
+    CHECK_LAUNCH();
+    k_merge_tile_scan<<<1, kScanThreads, 0, s>>>(sums, ntiles, totals);
+    CHECK_LAUNCH();
+    uint64_t tot[kMergeTotals] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(tot, totals, sizeof tot, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *n_out = tot[0];
+    *key_bytes_out = tot[1];
+    *value_bytes_out = tot[2];
+    if (tot[0] + 1 > offsets_cap)
+        return fail(PBF_ERR_INVALID, "the run holds " + std::to_string(tot[0]) + " records: each offsets array needs " +
+                                         std::to_string(tot[0] + 1) + " entries, offsets_cap is " +
+                                         std::to_string(offsets_cap));
+    if (tot[1] > keys_cap || (tot[1] && !keys_out))
+        return fail(PBF_ERR_INVALID, "the keys need " + std::to_string(tot[1]) + " bytes, keys_out holds " +
+                                         std::to_string(keys_out ? keys_cap : 0));
+    if (tot[2] > values_cap || (tot[2] && !values_out))
+        return fail(PBF_ERR_INVALID, "the values need " + std::to_string(tot[2]) + " bytes, values_out holds " +
+                                         std::to_string(values_out ? values_cap : 0));
+    uint8_t *dk = keys_out, *dv = values_out;
+    uint64_t *dko = key_offsets_out, *dvo = value_offsets_out;
+    if (!on_device) {
+        HIP_TRY(c.mkeys.ensure(tot[1] + 16));
+        HIP_TRY(c.mvals.ensure(tot[2] + 16));
+        HIP_TRY(c.mko.ensure((tot[0] + 1) * 8));
+        HIP_TRY(c.mvo.ensure((tot[0] + 1) * 8));
+        dk = static_cast<uint8_t*>(c.mkeys.p);
+        dv = static_cast<uint8_t*>(c.mvals.p);
+        dko = static_cast<uint64_t*>(c.mko.p);
+        dvo = static_cast<uint64_t*>(c.mvo.p);
+    }
+    k_merge_offsets<<<uint32_t(ntiles), kScanThreads, 0, s>>>(slots, n, sums, ntiles, pos, dko, dvo);
+    CHECK_LAUNCH();
+    k_merge_copy<<<grid_for(n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(set, slots, n, pos, totals, dko, dvo, dk, dv);
+    CHECK_LAUNCH();
+    if (on_device) {
+        if (!c.merge_done) HIP_TRY(hipEventCreateWithFlags(&c.merge_done, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c.merge_done, s));
+        return locks.used_on(s);
+    }
+    HIP_TRY(hipMemcpyAsync(key_offsets_out, dko, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(value_offsets_out, dvo, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (tot[1]) HIP_TRY(hipMemcpyAsync(keys_out, dk, tot[1], hipMemcpyDeviceToHost, s));
+    if (tot[2]) HIP_TRY(hipMemcpyAsync(values_out, dv, tot[2], hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return PBF_OK;
 }
 

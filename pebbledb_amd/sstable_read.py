@@ -231,5 +231,11 @@ class DeviceSSTable:
         found, values, _ = self.get_many([key])
         return values.tobytes() if found[0] else None
 
+    def records(self):
+        """SSTableIterator(sstable) (src/iterators.py:110-141) as a PackedRecords: every record
+        in key order (the one-table merge of ``compaction.merge_tables``)."""
+        from .compaction import merge_tables
+        return merge_tables([self])
+
     def __repr__(self):
         return f"DeviceSSTable(nblocks={self.nblocks}, nrecords={self.nrecords}, device={self.device})"
