@@ -422,6 +422,42 @@ int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint
                   uint64_t offsets_cap, uint64_t* n_out, uint64_t* key_bytes_out, uint64_t* value_bytes_out,
                   int on_device, void* stream);
 
+/* ---- Range scan over resident tables: SSTable.scan (src/sstable.py:189, the bounded
+ * SSTableIterator of src/iterators.py:58-141) and the MergingIterator LsmStorage.scan yields from
+ * (src/lsm_storage.py:187-190), for a batch of ranges in one call.
+ * Range q is [lower_q, upper_q], inclusive at both ends, compared as unsigned bytes: bound q =
+ * lowers[lower_offsets[q], lower_offsets[q+1]) and likewise uppers (offsets arrays of nranges + 1
+ * ascending entries).  lower > upper selects nothing; an empty lower starts at the first record.
+ * upper_open (NULL, or nranges bytes): non-zero = no upper bound, uppers' entry is ignored (the
+ * reference reads upper == "" that way).  tables[0] is the first iterator; per range the result
+ * is PBF_MERGE_DEDUP's run over the records in range.  The ranges are host memory in both calls.
+ * At most 64 tables and nranges * ntables <= PBF_SCAN_MAX_SEGMENTS. */
+#define PBF_SCAN_MAX_SEGMENTS (1ull << 22)
+
+/* Counts a batch (synchronous, host outputs): *n_in, *key_bytes_in, *value_bytes_in = the records
+ * in range over all tables and ranges and their key and value bytes BEFORE de-duplication: they
+ * always suffice as pbf_sst_scan's capacities (offsets_cap = *n_in + 1) and are exact when no key
+ * repeats across tables.  seg_lo_out / seg_hi_out (each NULL, or nranges * ntables entries, index
+ * q * ntables + t): table t's records [lo, hi) lie in range q. */
+int pbf_sst_scan_size(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* lowers,
+                      const uint64_t* lower_offsets, const uint8_t* uppers, const uint64_t* upper_offsets,
+                      const uint8_t* upper_open, uint64_t nranges, uint32_t* seg_lo_out, uint32_t* seg_hi_out,
+                      uint64_t* n_in, uint64_t* key_bytes_in, uint64_t* value_bytes_in);
+
+/* The run: the ranges' records back to back in pbf_sst_merge's layout (outputs, capacities, totals,
+ * on_device and stream as there), range q = records [range_offsets_out[q], range_offsets_out[q+1])
+ * of it.  range_offsets_out receives nranges + 1 entries and is host or device memory as the other
+ * outputs are.  A record that lies in two ranges appears in both.  nranges == 0: PBF_OK, an empty
+ * run (both offsets arrays = {0}, range_offsets_out[0] = 0).
+ * PBF_ERR_INVALID, nothing written to the outputs: as pbf_sst_merge, and more ranges x tables than
+ * PBF_SCAN_MAX_SEGMENTS. */
+int pbf_sst_scan(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* lowers, const uint64_t* lower_offsets,
+                 const uint8_t* uppers, const uint64_t* upper_offsets, const uint8_t* upper_open, uint64_t nranges,
+                 uint8_t* keys_out, uint64_t keys_cap, uint64_t* key_offsets_out, uint8_t* values_out,
+                 uint64_t values_cap, uint64_t* value_offsets_out, uint64_t offsets_cap, uint64_t* n_out,
+                 uint64_t* key_bytes_out, uint64_t* value_bytes_out, uint64_t* range_offsets_out, int on_device,
+                 void* stream);
+
 /* Synthetic keys straight into device memory (bench / tests; definitions in
  * pebbledb_amd/keys.py): 16 hex chars of splitmix64(seed + start + i), and the variable-length
  * 8..64-byte family (offsets must already hold the n+1 offsets, relative to offsets[0]).

@@ -6,7 +6,9 @@ hand-written HIP kernels for gfx950 in ``libpebblebloom.so`` (C-ABI: include/peb
 from .bloom_filter import BloomFilter, may_contain_multi, may_contain_set, probe_multi_device, set_default_device
 from .compaction import compact_l0, compact_level, concat_tables, merge_tables
 from .keys import PackedKeys
+from .lsm_scan import count_ranges, scan_ranges, scan_tables
 from .sstable_read import DeviceSSTable
 
 __all__ = ["BloomFilter", "DeviceSSTable", "PackedKeys", "compact_l0", "compact_level", "concat_tables",
-           "may_contain_multi", "may_contain_set", "merge_tables", "probe_multi_device", "set_default_device"]
+           "count_ranges", "may_contain_multi", "may_contain_set", "merge_tables", "probe_multi_device",
+           "scan_ranges", "scan_tables", "set_default_device"]

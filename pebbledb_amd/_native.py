@@ -90,6 +90,10 @@ SIGNATURES = {
     "pbf_sst_gather": (_int, [_vp, _u32, _vp, _vp, _vp, _u64, _u8p, _u64, _vp, _int, _vp]),
     "pbf_sst_merge": (_int, [_vp, _u32, _int, _u8p, _u64, _vp, _u8p, _u64, _vp, _u64, ctypes.POINTER(_u64),
                              ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _vp]),
+    "pbf_sst_scan_size": (_int, [_vp, _u32, _u8p, _vp, _u8p, _vp, _u8p, _u64, _vp, _vp, ctypes.POINTER(_u64),
+                                 ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "pbf_sst_scan": (_int, [_vp, _u32, _u8p, _vp, _u8p, _vp, _u8p, _u64, _u8p, _u64, _vp, _u8p, _u64, _vp, _u64,
+                            ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _int, _vp]),
     "pbf_gen_splitmix_hex": (_int, [_int, _vp, _u8p, _u64, _u64, _u64]),
     "pbf_gen_varlen": (_int, [_int, _vp, _u8p, _vp, _u64, _u64, _u64]),
     "pbf_last_error": (ctypes.c_char_p, []),

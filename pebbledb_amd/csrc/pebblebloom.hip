@@ -36,6 +36,7 @@
 #include "reader_service.hpp"
 #include "sstable_read_kernels.hpp"
 #include "sstable_merge_kernels.hpp"
+#include "sstable_scan_kernels.hpp"
 
 using namespace pbf;
 
@@ -3615,6 +3616,8 @@ struct SstCtx {
     // asynchronous call, which the next one waits for before it reuses them
     DevBuf mslots, mpos, msums, mkeys, mvals, mko, mvo;
     hipEvent_t merge_done = nullptr;
+    // pbf_sst_scan's bounds, segment arrays and (host form) range offsets: under merge_done too
+    DevBuf sbnd, sseg, sro;
 };
 
 SstCtx& sst_ctx(int device) {
@@ -4101,6 +4104,270 @@ int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint
     }
     HIP_TRY(hipMemcpyAsync(key_offsets_out, dko, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(value_offsets_out, dvo, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (tot[1]) HIP_TRY(hipMemcpyAsync(keys_out, dk, tot[1], hipMemcpyDeviceToHost, s));
+    if (tot[2]) HIP_TRY(hipMemcpyAsync(values_out, dv, tot[2], hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return PBF_OK;
+}
+
+}  // extern "C"
+
+// ====================================================================== range scan
+// SSTable.scan / the MergingIterator of LsmStorage.scan over resident tables, for a batch of
+// ranges (csrc/sstable_scan_kernels.hpp).
+namespace {
+
+constexpr uint64_t kScanMaxSegments = PBF_SCAN_MAX_SEGMENTS;
+
+// The ranges of a batch as the caller states them (host memory).
+struct ScanArgs {
+    const uint8_t *lowers, *uppers, *upper_open;
+    const uint64_t *lower_offsets, *upper_offsets;
+    uint64_t nranges;
+};
+
+// The segments of a batch in the context's working memory; n = the selected input records.
+struct ScanSegments {
+    MergeSet set{};
+    uint64_t nseg = 0, n = 0;
+    uint64_t* seg_base = nullptr;
+    uint32_t *seg_lo = nullptr, *seg_cnt = nullptr;
+};
+
+size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
+
+// The checks that need no device: the table list and the ranges.
+int scan_check(pbf_sstable_t* const* tables, uint32_t ntables, const ScanArgs& a) {
+    if (!tables || ntables == 0) return fail(PBF_ERR_INVALID, "no tables");
+    if (ntables > kSstTablesPerLaunch)
+        return fail(PBF_ERR_INVALID, "a scan takes at most " + std::to_string(kSstTablesPerLaunch) + " tables, got " +
+                                         std::to_string(ntables));
+    std::vector<pbf_sstable_t*> u(tables, tables + ntables);
+    std::sort(u.begin(), u.end());
+    if (std::adjacent_find(u.begin(), u.end()) != u.end()) return fail(PBF_ERR_INVALID, "the same table is listed twice");
+    if (a.nranges == 0) return PBF_OK;
+    if (a.nranges > kScanMaxSegments / ntables)
+        return fail(PBF_ERR_INVALID, "a scan takes at most " + std::to_string(kScanMaxSegments) +
+                                         " ranges x tables, got " + std::to_string(a.nranges) + " x " +
+                                         std::to_string(ntables));
+    if (!a.lower_offsets || !a.upper_offsets) return fail(PBF_ERR_INVALID, "null pointer");
+    for (const uint64_t* o : {a.lower_offsets, a.upper_offsets})
+        for (uint64_t q = 0; q < a.nranges; ++q) {
+            if (o[q + 1] < o[q]) return fail(PBF_ERR_INVALID, "bound offsets must ascend");
+            if (o[q + 1] - o[q] > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "a bound is longer than any key");
+        }
+    if ((a.lower_offsets[a.nranges] > a.lower_offsets[0] && !a.lowers) ||
+        (a.upper_offsets[a.nranges] > a.upper_offsets[0] && !a.uppers))
+        return fail(PBF_ERR_INVALID, "null pointer");
+    return PBF_OK;
+}
+
+// Steps 1 and 2 on `s`: uploads the bounds, k_scan_bounds, the exclusive scan of the counts, and
+// reads N back (one sync).  The caller holds the tables' locks and the context's, and has waited
+// for merge_done.
+int scan_segments(SstCtx& c, hipStream_t s, pbf_sstable_t* const* tables, uint32_t ntables, const ScanArgs& a,
+                  ScanSegments& g) {
+    int rc;
+    g.set.nt = ntables;
+    uint64_t nrec = 0;
+    for (uint32_t t = 0; t < ntables; ++t) {
+        pbf_sstable_t* tb = tables[t];
+        if ((rc = sst_rec_base(tb))) return rc;
+        g.set.data[t] = static_cast<const uint8_t*>(tb->data.p);
+        g.set.index[t] = static_cast<const SstBlock*>(tb->index.p);
+        g.set.last_prefix[t] = static_cast<const uint64_t*>(tb->prefix.p);
+        g.set.rec_base[t] = static_cast<const uint32_t*>(tb->rec_base.p);
+        g.set.nblocks[t] = tb->nblocks;
+        g.set.in_base[t] = nrec;
+        nrec += tb->nrecords;
+    }
+    const uint64_t Q = a.nranges;
+    g.nseg = Q * ntables;
+    g.n = 0;
+    if (g.nseg == 0) return PBF_OK;
+    // bounds: lower offsets ‖ upper offsets ‖ upper_open ‖ lower bytes ‖ upper bytes
+    const uint64_t lbytes = a.lower_offsets[Q] - a.lower_offsets[0], ubytes = a.upper_offsets[Q] - a.upper_offsets[0];
+    const size_t o_uo = (Q + 1) * 8, o_open = 2 * (Q + 1) * 8, o_lb = o_open + align16(Q), o_ub = o_lb + align16(lbytes);
+    HIP_TRY(c.sbnd.ensure(o_ub + align16(ubytes) + 16));
+    auto* bp = static_cast<uint8_t*>(c.sbnd.p);
+    HIP_TRY(hipMemcpyAsync(bp, a.lower_offsets, (Q + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(bp + o_uo, a.upper_offsets, (Q + 1) * 8, hipMemcpyHostToDevice, s));
+    if (a.upper_open) HIP_TRY(hipMemcpyAsync(bp + o_open, a.upper_open, Q, hipMemcpyHostToDevice, s));
+    if (lbytes) HIP_TRY(hipMemcpyAsync(bp + o_lb, a.lowers + a.lower_offsets[0], lbytes, hipMemcpyHostToDevice, s));
+    if (ubytes) HIP_TRY(hipMemcpyAsync(bp + o_ub, a.uppers + a.upper_offsets[0], ubytes, hipMemcpyHostToDevice, s));
+    ScanBounds b{};
+    b.lower_offsets = reinterpret_cast<const uint64_t*>(bp);
+    b.upper_offsets = reinterpret_cast<const uint64_t*>(bp + o_uo);
+    b.upper_open = a.upper_open ? bp + o_open : nullptr;
+    b.lowers = bp + o_lb;
+    b.uppers = bp + o_ub;
+    // segments: seg_base[nseg+1] ‖ tile sums ‖ seg_lo ‖ seg_cnt
+    const uint64_t stiles = (g.nseg + kScanTile - 1) / kScanTile;
+    HIP_TRY(c.sseg.ensure((g.nseg + 1 + stiles) * 8 + 2 * g.nseg * 4));
+    g.seg_base = static_cast<uint64_t*>(c.sseg.p);
+    uint64_t* sums = g.seg_base + g.nseg + 1;
+    g.seg_lo = reinterpret_cast<uint32_t*>(sums + stiles);
+    g.seg_cnt = g.seg_lo + g.nseg;
+    k_scan_bounds<<<grid_for(g.nseg, 256, 1u << 20), 256, 0, s>>>(g.set, b, g.nseg, g.seg_lo, g.seg_cnt);
+    CHECK_LAUNCH();
+    // (a count is below 2^31: the length scan reads it as a non-negative i32)
+    const int32_t* cnt = reinterpret_cast<const int32_t*>(g.seg_cnt);
+    k_len_tile_sums<<<uint32_t(stiles), kScanThreads, 0, s>>>(cnt, g.nseg, sums);
+    CHECK_LAUNCH();
+    k_len_tile_scan<<<1, kScanThreads, 0, s>>>(sums, stiles);
+    CHECK_LAUNCH();
+    k_len_offsets<<<uint32_t(stiles), kScanThreads, 0, s>>>(cnt, g.nseg, sums, g.seg_base);
+    CHECK_LAUNCH();
+    HIP_TRY(hipMemcpyAsync(&g.n, g.seg_base + g.nseg, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return PBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbf_sst_scan_size(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* lowers,
+                      const uint64_t* lower_offsets, const uint8_t* uppers, const uint64_t* upper_offsets,
+                      const uint8_t* upper_open, uint64_t nranges, uint32_t* seg_lo_out, uint32_t* seg_hi_out,
+                      uint64_t* n_in, uint64_t* key_bytes_in, uint64_t* value_bytes_in) {
+    const ScanArgs a{lowers, uppers, upper_open, lower_offsets, upper_offsets, nranges};
+    int rc = scan_check(tables, ntables, a);
+    if (rc) return rc;
+    if (!n_in || !key_bytes_in || !value_bytes_in) return fail(PBF_ERR_INVALID, "null pointer");
+    SstLocks locks;
+    if ((rc = locks.take(tables, ntables))) return rc;
+    const int device = tables[0]->device;
+    HIP_TRY(hipSetDevice(device));
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    if ((rc = sst_ctx_stream(c, device))) return rc;
+    if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
+    hipStream_t s = c.stream;
+    ScanSegments g;
+    if ((rc = scan_segments(c, s, tables, ntables, a, g))) return rc;
+    unsigned long long tot[kScanSizeTotals] = {0, 0};
+    if (g.n) {
+        HIP_TRY(c.msums.ensure(sizeof tot));
+        auto* totals = static_cast<unsigned long long*>(c.msums.p);
+        HIP_TRY(hipMemsetAsync(totals, 0, sizeof tot, s));
+        k_scan_sizes<<<grid_for(g.n, kScanThreads, 4096), kScanThreads, 0, s>>>(g.set, g.seg_base, g.seg_lo, g.nseg, g.n,
+                                                                                totals);
+        CHECK_LAUNCH();
+        HIP_TRY(hipMemcpyAsync(tot, totals, sizeof tot, hipMemcpyDeviceToHost, s));
+    }
+    std::vector<uint32_t> lo;
+    if (g.nseg && (seg_lo_out || seg_hi_out)) {
+        lo.resize(g.nseg);
+        HIP_TRY(hipMemcpyAsync(lo.data(), g.seg_lo, g.nseg * 4, hipMemcpyDeviceToHost, s));
+        if (seg_hi_out) HIP_TRY(hipMemcpyAsync(seg_hi_out, g.seg_cnt, g.nseg * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < lo.size(); ++i) {
+        if (seg_lo_out) seg_lo_out[i] = lo[i];
+        if (seg_hi_out) seg_hi_out[i] += lo[i];  // the count becomes the window's end
+    }
+    *n_in = g.n;
+    *key_bytes_in = tot[0];
+    *value_bytes_in = tot[1];
+    return PBF_OK;
+}
+
+int pbf_sst_scan(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* lowers, const uint64_t* lower_offsets,
+                 const uint8_t* uppers, const uint64_t* upper_offsets, const uint8_t* upper_open, uint64_t nranges,
+                 uint8_t* keys_out, uint64_t keys_cap, uint64_t* key_offsets_out, uint8_t* values_out,
+                 uint64_t values_cap, uint64_t* value_offsets_out, uint64_t offsets_cap, uint64_t* n_out,
+                 uint64_t* key_bytes_out, uint64_t* value_bytes_out, uint64_t* range_offsets_out, int on_device,
+                 void* stream) {
+    const ScanArgs a{lowers, uppers, upper_open, lower_offsets, upper_offsets, nranges};
+    int rc = scan_check(tables, ntables, a);
+    if (rc) return rc;
+    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out || !range_offsets_out)
+        return fail(PBF_ERR_INVALID, "null pointer");
+    SstLocks locks;
+    if ((rc = locks.take(tables, ntables))) return rc;
+    const int device = tables[0]->device;
+    HIP_TRY(hipSetDevice(device));
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    if ((rc = sst_ctx_stream(c, device))) return rc;
+    if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
+    hipStream_t s = on_device ? static_cast<hipStream_t>(stream) : c.stream;
+    ScanSegments g;
+    if ((rc = scan_segments(c, s, tables, ntables, a, g))) return rc;
+    const uint64_t n = g.n, ntiles = (n + kScanTile - 1) / kScanTile;
+    if (ntiles > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "run too large");
+    MergeSlot* slots = nullptr;
+    uint64_t *pos = nullptr, *sums = nullptr, *totals = nullptr;
+    uint64_t tot[kMergeTotals] = {0, 0, 0};
+    if (n) {
+        HIP_TRY(c.mslots.ensure(n * sizeof(MergeSlot)));
+        HIP_TRY(c.mpos.ensure(n * 8));
+        HIP_TRY(c.msums.ensure((kMergeTotals * ntiles + kMergeTotals) * 8));
+        slots = static_cast<MergeSlot*>(c.mslots.p);
+        pos = static_cast<uint64_t*>(c.mpos.p);
+        sums = static_cast<uint64_t*>(c.msums.p);
+        totals = sums + kMergeTotals * ntiles;
+        // (a slot no record claims stays dropped: the ranks are a permutation, this is the belt)
+        HIP_TRY(hipMemsetAsync(slots, 0, n * sizeof(MergeSlot), s));
+        k_scan_rank<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(g.set, g.seg_base, g.seg_lo, g.seg_cnt, g.nseg, n, slots);
+        CHECK_LAUNCH();
+        k_merge_tile_sums<<<uint32_t(ntiles), kScanThreads, 0, s>>>(slots, n, sums, ntiles);
+        CHECK_LAUNCH();
+        k_merge_tile_scan<<<1, kScanThreads, 0, s>>>(sums, ntiles, totals);
+        CHECK_LAUNCH();
+        HIP_TRY(hipMemcpyAsync(tot, totals, sizeof tot, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    *n_out = tot[0];
+    *key_bytes_out = tot[1];
+    *value_bytes_out = tot[2];
+    if (tot[0] + 1 > offsets_cap)
+        return fail(PBF_ERR_INVALID, "the run holds " + std::to_string(tot[0]) + " records: each offsets array needs " +
+                                         std::to_string(tot[0] + 1) + " entries, offsets_cap is " +
+                                         std::to_string(offsets_cap));
+    if (tot[1] > keys_cap || (tot[1] && !keys_out))
+        return fail(PBF_ERR_INVALID, "the keys need " + std::to_string(tot[1]) + " bytes, keys_out holds " +
+                                         std::to_string(keys_out ? keys_cap : 0));
+    if (tot[2] > values_cap || (tot[2] && !values_out))
+        return fail(PBF_ERR_INVALID, "the values need " + std::to_string(tot[2]) + " bytes, values_out holds " +
+                                         std::to_string(values_out ? values_cap : 0));
+    uint8_t *dk = keys_out, *dv = values_out;
+    uint64_t *dko = key_offsets_out, *dvo = value_offsets_out, *dro = range_offsets_out;
+    if (!on_device) {
+        HIP_TRY(c.mkeys.ensure(tot[1] + 16));
+        HIP_TRY(c.mvals.ensure(tot[2] + 16));
+        HIP_TRY(c.mko.ensure((tot[0] + 1) * 8));
+        HIP_TRY(c.mvo.ensure((tot[0] + 1) * 8));
+        HIP_TRY(c.sro.ensure((nranges + 1) * 8));
+        dk = static_cast<uint8_t*>(c.mkeys.p);
+        dv = static_cast<uint8_t*>(c.mvals.p);
+        dko = static_cast<uint64_t*>(c.mko.p);
+        dvo = static_cast<uint64_t*>(c.mvo.p);
+        dro = static_cast<uint64_t*>(c.sro.p);
+    }
+    if (n) {
+        k_merge_offsets<<<uint32_t(ntiles), kScanThreads, 0, s>>>(slots, n, sums, ntiles, pos, dko, dvo);
+        CHECK_LAUNCH();
+        k_merge_copy<<<grid_for(n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(g.set, slots, n, pos, totals, dko, dvo, dk,
+                                                                              dv);
+        CHECK_LAUNCH();
+        k_scan_range_offsets<<<grid_for(nranges + 1, 256, 1u << 20), 256, 0, s>>>(g.seg_base, ntables, nranges, slots, n,
+                                                                                  pos, sums, totals, dro);
+        CHECK_LAUNCH();
+    } else {  // an empty run: both offsets arrays are {0}, every range is empty
+        HIP_TRY(hipMemsetAsync(dko, 0, 8, s));
+        HIP_TRY(hipMemsetAsync(dvo, 0, 8, s));
+        HIP_TRY(hipMemsetAsync(dro, 0, (nranges + 1) * 8, s));
+    }
+    if (on_device) {
+        if (!c.merge_done) HIP_TRY(hipEventCreateWithFlags(&c.merge_done, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c.merge_done, s));
+        return locks.used_on(s);
+    }
+    HIP_TRY(hipMemcpyAsync(key_offsets_out, dko, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(value_offsets_out, dvo, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(range_offsets_out, dro, (nranges + 1) * 8, hipMemcpyDeviceToHost, s));
     if (tot[1]) HIP_TRY(hipMemcpyAsync(keys_out, dk, tot[1], hipMemcpyDeviceToHost, s));
     if (tot[2]) HIP_TRY(hipMemcpyAsync(values_out, dv, tot[2], hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));

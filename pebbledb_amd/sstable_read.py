@@ -237,5 +237,12 @@ class DeviceSSTable:
         from .compaction import merge_tables
         return merge_tables([self])
 
+    def scan(self, lower: str, upper: str):
+        """SSTable.scan (sstable.py:189) as a PackedRecords: the records with ``lower <= key <=
+        upper`` in key order; ``upper == ""`` means no upper bound, as in the reference
+        (``lsm_scan.scan_tables`` over this one table)."""
+        from .lsm_scan import scan_tables
+        return scan_tables([self], lower, upper)
+
     def __repr__(self):
         return f"DeviceSSTable(nblocks={self.nblocks}, nrecords={self.nrecords}, device={self.device})"

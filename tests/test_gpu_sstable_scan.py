@@ -1,0 +1,636 @@
+"""The range scan over resident SSTables (pbf_sst_scan_size / pbf_sst_scan,
+csrc/sstable_scan_kernels.hpp; pebbledb_amd/lsm_scan.py): the reference's golden ranges end to
+end, then every branch of the bounds stage, the rank stage, the batch bookkeeping, the scans and
+the copy at the smallest shapes that enter it.  Expected runs come from tests/scan_model.py
+(pinned to the reference in tests/test_scan_model_cpu.py); tables no builder writes come from
+tests/sstable_raw.py."""
+import ctypes
+import hashlib
+import itertools
+import json
+import os
+
+import numpy as np
+import pytest
+
+from pebbledb_amd import DeviceSSTable, _native, lsm_get
+from pebbledb_amd.compaction import merge_tables
+from pebbledb_amd.lsm_scan import _Bounds, count_ranges, scan_ranges, scan_tables
+from pebbledb_amd.sstable_data import build_sstable
+
+import merge_model as MM
+import scan_model as SM
+import sstable_raw as R
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+vp = ctypes.c_void_p
+SCAN_TILE = 2048  # kScanTile: 256 threads x 8 slots
+GUARD = 0xA5
+GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "lsm_scan.json")
+CASES = json.load(open(GOLDEN, encoding="utf-8"))["cases"]
+
+
+@pytest.fixture
+def opened():
+    """Opens tables and closes what it opened: opened(rows, block_size) builds a table with the
+    library's builder from (str key, value) rows; opened.raw(blocks) opens a data section written
+    byte by byte from [[(key bytes, value bytes), ...], ...]."""
+    handles = []
+
+    def _open(rows, block_size=256):
+        f, _, _ = build_sstable([k for k, _ in rows], [v for _, v in rows], block_size)
+        handles.append(DeviceSSTable.from_bytes(f))
+        return handles[-1]
+
+    def _raw(blocks):
+        handles.append(R.open_raw(*R.raw_data_section(blocks)))
+        return handles[-1]
+
+    _open.raw = _raw
+    yield _open
+    for t in handles:
+        t.close()
+
+
+def records_of(pr):
+    """[(key bytes, value bytes)] of a PackedRecords."""
+    kb, vb = pr.keys.data.tobytes(), np.asarray(pr.values).tobytes()
+    ko, vo = pr.keys.offsets, pr.value_offsets
+    assert pr.keys.offsets is not None and len(ko) == len(vo) == pr.n + 1 and ko[0] == 0 and vo[0] == 0
+    assert int(ko[-1]) == len(kb) and int(vo[-1]) == len(vb)
+    return [(kb[int(ko[i]):int(ko[i + 1])], vb[int(vo[i]):int(vo[i + 1])]) for i in range(pr.n)]
+
+
+def model_runs(rows, ranges):
+    return [[(k, v) for k, v, _ in SM.scan(rows, lo, up)] for lo, up in ranges]
+
+
+def check_ranges(tables, rows, ranges):
+    """One scan_ranges call equals the model range by range; range_offsets ascend from 0 to n."""
+    want = model_runs(rows, ranges)
+    pr, ro = scan_ranges(tables, ranges)
+    got = records_of(pr)
+    assert ro.dtype == np.uint64 and len(ro) == len(ranges) + 1 and ro[0] == 0 and int(ro[-1]) == pr.n
+    assert all(int(a) <= int(b) for a, b in zip(ro, ro[1:]))
+    for q, w in enumerate(want):
+        assert got[int(ro[q]):int(ro[q + 1])] == w, (q, ranges[q])
+    return got, ro
+
+
+def size_call(tables, ranges):
+    """pbf_sst_scan_size: (lo[Q, T], hi[Q, T], n, key bytes, value bytes)."""
+    b = _Bounds(ranges)
+    hs = (vp * len(tables))(*[t._h.value for t in tables])
+    lo = np.full((b.n, len(tables)), 0xFFFFFFFF, dtype=np.uint32)
+    hi = np.full((b.n, len(tables)), 0xFFFFFFFF, dtype=np.uint32)
+    tot = [ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()]
+    rc = _native.lib().pbf_sst_scan_size(hs, len(tables), *b.args(), vp(lo.ctypes.data), vp(hi.ctypes.data),
+                                         *[ctypes.byref(x) for x in tot])
+    _native.check(rc, "pbf_sst_scan_size")
+    return lo, hi, tot[0].value, tot[1].value, tot[2].value
+
+
+def check_bounds(tables, rows, ranges):
+    """The bounds stage alone: every segment's [lo, hi) is bisect's over the table's key bytes."""
+    want = np.array([SM.windows(rows, lo, up) for lo, up in ranges], dtype=np.int64).reshape(len(ranges), len(rows), 2)
+    lo, hi, n, kb, vb = size_call(tables, ranges)
+    bad = np.argwhere((lo != want[:, :, 0]) | (hi != want[:, :, 1]))
+    assert not len(bad), [(ranges[q], int(t), (int(lo[q, t]), int(hi[q, t])), tuple(want[q, t])) for q, t in bad[:5]]
+    assert np.array_equal(count_ranges(tables, ranges), want[:, :, 1] - want[:, :, 0])
+    sums = [SM.presum(rows, a, b) for a, b in ranges]
+    assert (n, kb, vb) == tuple(sum(s[i] for s in sums) for i in range(3))
+
+
+def value(tag: int, i: int, n: int = None) -> bytes:
+    return MM.value_of(tag * 1000 + i, 1 + (tag * 5 + i) % 23 if n is None else n)
+
+
+def rows_of(tag: int, idx, key="k{i:05d}"):
+    """Rows whose values name their table."""
+    return [(key.format(i=i), value(tag, i)) for i in idx]
+
+
+def k(i: int) -> str:
+    return f"k{i:05d}"
+
+
+def all_pairs(bounds):
+    return [(a, b) for a in bounds for b in bounds]
+
+
+# ------------------------------------------------------------------ golden cases
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_golden_case_end_to_end(opened, case):
+    """The reference's ranges: stream hashes and the source table of every record (its value is
+    the one that table stores for its key) through scan_tables per range, then all the ranges in
+    one scan_ranges call, and every table's own window through count_ranges and t.scan."""
+    rows = MM.case_tables(case)
+    tables = [opened(r, case["table_block_size"]) for r in rows]
+    assert [t.nblocks for t in tables] == case["blocks"]
+    stored = [dict(r) for r in rows]
+    ranges = [(r["lower"], r["upper"]) for r in case["ranges"]]
+    runs = []
+    for r in case["ranges"]:
+        got = records_of(scan_tables(tables, r["lower"], r["upper"]))
+        runs.append(got)
+        assert len(got) == r["records"], r["name"]
+        assert hashlib.sha256(b"".join(x for x, _ in got)).hexdigest() == r["keys_sha256"], r["name"]
+        assert hashlib.sha256(b"".join(v for _, v in got)).hexdigest() == r["values_sha256"], r["name"]
+        sources = [t for t, c in r["source_runs"] for _ in range(c)]
+        assert len(sources) == len(got)
+        for (key, v), t in zip(got, sources):
+            assert stored[t][key.decode()] == v, (r["name"], key, t)
+    pr, ro = scan_ranges(tables, ranges)
+    got = records_of(pr)
+    assert [int(x) for x in ro] == [0] + list(itertools.accumulate(r["records"] for r in case["ranges"]))
+    for q, run in enumerate(runs):
+        assert got[int(ro[q]):int(ro[q + 1])] == run
+    assert count_ranges(tables, ranges).tolist() == [r["table_records"] for r in case["ranges"]]
+    r = case["ranges"][0]
+    for t, table in enumerate(tables):
+        assert records_of(table.scan(r["lower"], r["upper"])) == SM.scan_one(rows[t], r["lower"], r["upper"])
+        assert table.scan(r["lower"], r["upper"]).n == r["table_records"][t]
+
+
+# ------------------------------------------------------------------ bounds stage
+def seam_blocks():
+    return [[(f"m{b}{j}".encode(), value(7, 10 * b + j)) for j in range(2, 8)] for b in range(5)]
+
+
+def seam_bounds():
+    bounds = ["a", "m0", "m01", "m02"]                     # below the first key m02, and the first key
+    for b in range(4):
+        bounds += [f"m{b}7",                               # a block's last key (the next block's previous last key)
+                   f"m{b}7x", f"m{b}9",                    # strictly between two blocks
+                   f"m{b + 1}2",                           # the next block's first key
+                   f"m{b + 1}4"]                           # inside a block
+    return sorted(set(bounds + ["m47", "m47z", "m5", "z"]))  # the last key, and above it
+
+
+def test_bounds_on_block_seams(opened):
+    """Every pairing of bounds that sit on a block's first key, its last key, the previous
+    block's last key, the next block's first key, between blocks, below the table's first key
+    and above its last — as lower and as upper, inverted pairs included — against bisect; then
+    the runs of those ranges over the table and a second one."""
+    blocks = seam_blocks()
+    rows = [(x.decode(), v) for blk in blocks for x, v in blk]
+    t = opened.raw(blocks)
+    ranges = all_pairs(seam_bounds()) + [("", b) for b in seam_bounds()] + [(b, "") for b in seam_bounds()]
+    check_bounds([t], [rows], ranges)
+    other = [(x, value(8, i)) for i, x in enumerate(seam_bounds())]
+    u = opened(other, 64)
+    assert u.nblocks > 1
+    check_bounds([t, u], [rows, other], ranges)
+    check_ranges([u, t], [other, rows], ranges)
+
+
+def test_one_record_blocks_and_one_block_tables(opened):
+    single = [(k(i), value(2, i, 4)) for i in range(0, 60, 2)]
+    u = opened(single, 8 + 6 + 4)  # a block is full with one record
+    assert u.nblocks == u.nrecords == 30
+    one_block = rows_of(1, range(1, 41, 3))
+    t = opened(one_block, 65_536)
+    assert t.nblocks == 1
+    bounds = ["", "k", k(0), k(1), k(2), k(3), k(30), k(31), k(39), k(40), k(41), k(58), k(59), "k00058x", "l"]
+    ranges = all_pairs(bounds)
+    check_bounds([u, t], [single, one_block], ranges)
+    check_ranges([u, t], [single, one_block], ranges)
+    check_ranges([t], [one_block], ranges)
+
+
+def ab_strings():
+    return sorted("shared__" + "".join(s) for n in range(9) for s in itertools.product("ab", repeat=n))
+
+
+def test_bounds_prefix_tie_path(opened):
+    """Every stored key shares its first 8 bytes: several blocks' last-key prefixes tie with
+    every bound's, so the block search compares records.  Bounds longer than 8 bytes (stored,
+    absent, proper prefixes of stored keys and extensions of them), of exactly 8 and of 7."""
+    keys = ab_strings()
+    rows = [[(x, value(t, i)) for i, x in enumerate(keys) if i % 3 == t or i % 7 == 0] for t in range(3)]
+    tables = [opened(r, 160) for r in rows]
+    assert min(t.nblocks for t in tables) > 4
+    assert len({R.key_prefix(x.encode()) for x in keys}) == 1
+    bounds = ["shared_", "shared__", "shared__a", "shared__aab", "shared__aabz", "shared__ab", "shared__abababab",
+              "shared__abababab0", "shared__abb", "shared__b", "shared__bbbbbbbb", "shared__bbbbbbbbb", "shared__c",
+              "shared_a", "shared`"]
+    ranges = all_pairs(bounds)
+    check_bounds(tables, rows, ranges)
+    check_ranges(tables, rows, ranges)
+
+
+def test_high_bytes_against_non_ascii_bounds(opened):
+    """Raw tables whose keys hold bytes >= 0x80, scanned with non-ASCII str bounds: a bound is
+    its UTF-8 bytes, compared unsigned (a signed compare would put these keys first)."""
+    e, euro = "é".encode(), "€".encode()
+    keys = sorted({b"\x7f", b"\x80", b"\xc3", b"\xc3\xa8", e, e + b"\x00", e + b"tail-past-8-bytes", b"\xc3\xbf",
+                   b"\xe2\x82", euro, euro + b"\xff", b"\xff", b"\xff" * 9, b"prefix-\x80", b"prefix-0", b"prefix-0\x80",
+                   b"a", b"z"})
+    rows = [[(x, value(t, i)) for i, x in enumerate(keys) if (i + t) % 3 != 0] for t in range(3)]
+    tables = [opened.raw(R.split_blocks([x for x, _ in r], [v for _, v in r], 60)) for r in rows]
+    bounds = ["", "a", "z", "\x7f", "\x80", "è", "é", "é\x00", "étail", "ÿ", "€", "€€", "prefix-0", "prefix-\x80",
+              "\U0010ffff"]
+    ranges = all_pairs(bounds)
+    check_bounds(tables, rows, ranges)
+    got, ro = check_ranges(tables, rows, ranges)
+    q = ranges.index(("é", "€"))
+    assert [x for x, _ in got[int(ro[q]):int(ro[q + 1])]] == [x for x in keys if e <= x <= euro]
+
+
+def test_empty_key_stored(opened):
+    """The zero-length key is a table's first record: lower == "" starts on it."""
+    a = [("", b"newest"), ("b", b"1")]
+    b = [("", b"older"), ("a", b""), ("c", b"3")]
+    tables, rows = [opened(a, 64), opened(b, 64)], [a, b]
+    ranges = [("", ""), ("", "a"), ("", "b"), ("a", ""), ("a", "a"), ("\x00", ""), ("", "\x00")]
+    check_bounds(tables, rows, ranges)
+    got, ro = check_ranges(tables, rows, ranges)
+    assert got[:int(ro[1])] == [(b"", b"newest"), (b"a", b""), (b"b", b"1"), (b"c", b"3")]
+    assert got[int(ro[1]):int(ro[2])] == [(b"", b"newest"), (b"a", b"")]
+    assert records_of(tables[1].scan("", "a")) == [(b"", b"older"), (b"a", b"")]
+
+
+# ------------------------------------------------------------------ rank stage
+@pytest.mark.parametrize("order", list(itertools.permutations(range(3))), ids=lambda o: "".join(map(str, o)))
+def test_range_empty_in_some_tables(opened, order):
+    """Tables whose window is empty are not searched (the skip path): the empty table first, in
+    the middle and last, for windows empty because the table lies below the range, above it, or
+    has a gap there."""
+    base = [rows_of(0, range(0, 100)), rows_of(1, list(range(200, 300)) + list(range(400, 420))),
+            rows_of(2, range(50, 450, 3))]
+    rows = [base[i] for i in order]
+    tables = [opened(r, 128) for r in rows]
+    ranges = [(k(0), k(150)),      # table 1 empty (above)
+              (k(120), k(199)),    # tables 0 and 1 empty (below / above)
+              (k(300), k(399)),    # table 1 empty in its gap, table 0 below
+              (k(250), k(500)),    # table 0 empty
+              (k(100), k(100)), (k(460), ""), ("", k(49))]
+    counts = count_ranges(tables, ranges)
+    assert (counts[:4] == 0).any(axis=1).all() and (counts[:4] > 0).any(axis=1).all()
+    check_bounds(tables, rows, ranges)
+    check_ranges(tables, rows, ranges)
+
+
+def test_duplicates_at_the_bounds(opened):
+    """A key stored in several tables at exactly lower and at exactly upper: the lowest table
+    index wins, the losers are not kept — also when the winner's window holds that key alone."""
+    rows = [rows_of(0, [10, 20, 30, 40]), rows_of(1, [5, 10, 25, 40, 45]), rows_of(2, [10, 15, 40, 50])]
+    tables = [opened(r, 64) for r in rows]
+    got, ro = check_ranges(tables, rows, [(k(10), k(40)), (k(10), k(10)), (k(40), k(40)), (k(40), ""), ("", k(10))])
+    first = got[:int(ro[1])]
+    assert first[0] == (k(10).encode(), value(0, 10)) and first[-1] == (k(40).encode(), value(0, 40))
+    assert [x for x, _ in first] == [k(i).encode() for i in (10, 15, 20, 25, 30, 40)]
+    assert got[int(ro[1]):int(ro[2])] == [(k(10).encode(), value(0, 10))]
+    rev = tables[::-1]
+    got, ro = check_ranges(rev, rows[::-1], [(k(10), k(40))])
+    assert got[0] == (k(10).encode(), value(2, 10)) and got[-1] == (k(40).encode(), value(2, 40))
+
+
+def test_every_key_in_every_table(opened):
+    rows = [rows_of(t, range(0, 200)) for t in range(4)]
+    tables = [opened(r, 96 + 32 * t) for t, r in enumerate(rows)]
+    ranges = [(k(0), k(199)), (k(50), k(60)), (k(199), ""), ("", k(0)), (k(77), k(77))]
+    got, ro = check_ranges(tables, rows, ranges)
+    assert got[:int(ro[1])] == [(x.encode(), v) for x, v in rows[0]]
+    assert count_ranges(tables, ranges).tolist() == [[200] * 4, [11] * 4, [1] * 4, [1] * 4, [1] * 4]
+
+
+def test_table_count_limits(opened):
+    """T = 1, T = 64, and T = 65 refused by the Python layer and by the library."""
+    rows = [sorted(set(rows_of(t, [t, t + 1, t + 64, 200 + (t * 7) % 13]))) for t in range(65)]
+    tables = [opened(r, 40) for r in rows]
+    ranges = [(k(0), k(300)), (k(30), k(70)), (k(64), k(64)), (k(200), ""), (k(129), k(199))]
+    check_ranges(tables[:1], rows[:1], ranges)
+    check_bounds(tables[:64], rows[:64], ranges)
+    check_ranges(tables[:64], rows[:64], ranges)
+    for fn in (scan_ranges, count_ranges):
+        with pytest.raises(ValueError, match="at most 64"):
+            fn(tables, ranges)
+    with pytest.raises(ValueError, match="at most 64"):
+        scan_tables(tables, "", "")
+    hs = (vp * 65)(*[t._h.value for t in tables])
+    z = ctypes.c_uint64()
+    L = _native.lib()
+    b = _Bounds(ranges)
+    rc = L.pbf_sst_scan(hs, 65, *b.args(), None, 0, None, None, 0, None, 0, ctypes.byref(z), ctypes.byref(z),
+                        ctypes.byref(z), None, 0, None)
+    assert rc == _native.PBF_ERR_INVALID and b"at most 64" in L.pbf_last_error()
+    rc = L.pbf_sst_scan_size(hs, 65, *b.args(), None, None, ctypes.byref(z), ctypes.byref(z), ctypes.byref(z))
+    assert rc == _native.PBF_ERR_INVALID and b"at most 64" in L.pbf_last_error()
+
+
+# ------------------------------------------------------------------ batches
+def three_tables(opened):
+    rows = [rows_of(0, range(0, 300, 3)), rows_of(1, range(0, 300, 2)), rows_of(2, range(100, 400, 5))]
+    return [opened(r, 128) for r in rows], rows
+
+
+def test_batches_overlapping_identical_descending_adjacent(opened):
+    tables, rows = three_tables(opened)
+    overlapping = [(k(0), k(120)), (k(60), k(200)), (k(100), k(110))]
+    identical = [(k(30), k(90))] * 3
+    descending = [(k(300), k(399)), (k(200), k(299)), (k(100), k(199)), (k(0), k(99))]
+    adjacent = [(k(90), k(150)), (k(150), k(210))]  # k00150 is stored: both ranges hold it
+    got, ro = check_ranges(tables, rows, overlapping + identical + descending + adjacent)
+    r = [got[int(ro[q]):int(ro[q + 1])] for q in range(len(ro) - 1)]
+    assert set(r[2]) <= set(r[0]) & set(r[1]) and r[2]               # the same records in two ranges
+    assert r[3] == r[4] == r[5] and r[3]
+    assert r[6][0][0] > r[9][-1][0]                                    # the run follows the ranges' order
+    assert r[10][-1] == r[11][0] == (k(150).encode(), value(0, 150))
+
+
+@pytest.mark.parametrize("where", ["first", "middle", "last", "all"])
+def test_empty_ranges(opened, where):
+    tables, rows = three_tables(opened)
+    empty = [(k(500), k(600)), (k(50), k(40)), ("k00001x", "k00001y"), ("l", "")]
+    full = [(k(10), k(20)), ("", k(5))]
+    ranges = {"first": empty + full, "middle": full[:1] + empty + full[1:], "last": full + empty, "all": empty}[where]
+    got, ro = check_ranges(tables, rows, ranges)
+    assert (len(got) == 0) == (where == "all")
+    lo, hi, n, kb, vb = size_call(tables, ranges)
+    assert (n == 0) == (where == "all")
+
+
+def test_many_ranges_span_several_segment_tiles(opened):
+    """Q = 700 ranges over T = 3 tables: 2100 segments, more than one scan tile of them; the
+    ranges overlap their neighbours, some are empty."""
+    tables, rows = three_tables(opened)
+    ranges = [(k(i % 400), k(i % 400 + (i * 7) % 23 - 2)) for i in range(700)]
+    assert len(ranges) * len(tables) > SCAN_TILE
+    check_bounds(tables, rows, ranges)
+    got, ro = check_ranges(tables, rows, ranges)
+    assert len(got) > 2000 and sum(int(a) == int(b) for a, b in zip(ro, ro[1:])) > 40
+
+
+def test_no_ranges(opened):
+    tables, rows = three_tables(opened)
+    pr, ro = scan_ranges(tables, [])
+    assert pr.n == 0 and ro.tolist() == [0] and records_of(pr) == []
+    assert count_ranges(tables, []).shape == (0, 3)
+    out = scan_call(tables, [], device=True)
+    assert out["rc"] == 0 and out["n"] == 0 and out["ko"][0] == 0 and out["vo"][0] == 0 and out["ro"][0] == 0
+
+
+# ------------------------------------------------------------------ scan edges
+@pytest.mark.parametrize("n", [SCAN_TILE - 1, SCAN_TILE, SCAN_TILE + 1])
+def test_scan_tile_edges(opened, n):
+    """N = 2047, 2048, 2049 selected records (two disjoint tables, so a range of keys i..j
+    selects j - i + 1 of them), as one range and split in two with the range boundary one slot
+    before the tile edge, on it, and one slot past it."""
+    a = rows_of(0, range(0, 2200, 2), "{i:07d}")
+    b = rows_of(1, range(1, 2200, 2), "{i:07d}")
+    tables, rows = [opened(a, 4096), opened(b, 4096)], [a, b]
+    key = "{:07d}".format
+    batches = [[(key(50), key(50 + n - 1))]]
+    for s in (SCAN_TILE - 1, SCAN_TILE, SCAN_TILE + 1):
+        if s < n:
+            batches.append([(key(50), key(50 + s - 1)), (key(50 + s), key(50 + n - 1))])
+    for ranges in batches:
+        assert size_call(tables, ranges)[2] == n
+        got, ro = check_ranges(tables, rows, ranges)
+        assert len(got) == n
+
+
+_BIG = {}
+
+
+def big_rows():
+    """Three tables of 180,000 records (16-byte keys, 1-byte values): 270,000 distinct keys, each
+    in two tables.  540,000 selected records are 264 scan tiles: past the 256 one pass of the
+    tile scan takes.  Built once."""
+    if not _BIG:
+        rows = [[(f"{i:016d}", bytes([(i * 7 + t) & 0xFF])) for i in range(270_000) if i % 3 != t] for t in range(3)]
+        _BIG.update(rows=rows, run=MM.merge(rows))
+    return _BIG
+
+
+def test_scan_past_the_carry_threshold(opened):
+    big = big_rows()
+    rows = big["rows"]
+    assert sum(len(r) for r in rows) == 540_000 > 524_288 and -(-540_000 // SCAN_TILE) > 256
+    tables = [opened(r, 65_536) for r in rows]
+    pr, ro = scan_ranges(tables, [("", "")])
+    want = big["run"]
+    assert pr.n == len(want) == 270_000 and ro.tolist() == [0, 270_000]
+    assert hashlib.sha256(pr.keys.data.tobytes()).hexdigest() == hashlib.sha256(b"".join(x for x, _, _ in want)).hexdigest()
+    assert hashlib.sha256(np.asarray(pr.values).tobytes()).hexdigest() == \
+        hashlib.sha256(b"".join(v for _, v, _ in want)).hexdigest()
+    assert np.array_equal(pr.keys.offsets, np.arange(pr.n + 1, dtype=np.uint64) * 16)
+    assert np.array_equal(pr.value_offsets, np.arange(pr.n + 1, dtype=np.uint64))
+
+
+# ------------------------------------------------------------------ the low-level call
+def scan_call(tables, ranges, keys_cap=None, values_cap=None, offsets_cap=None, device=False, shift=0):
+    """pbf_sst_scan with chosen capacities (default: pbf_sst_scan_size's totals) into buffers that
+    carry a guard pattern after the stated capacity (and `shift` bytes before the byte buffers'
+    start).  Returns the return code, message, totals and the five buffers (numpy), guards
+    included."""
+    b = _Bounds(ranges)
+    hs = (vp * len(tables))(*[t._h.value for t in tables])
+    _, _, n_in, kb_in, vb_in = size_call(tables, ranges)
+    keys_cap = kb_in if keys_cap is None else keys_cap
+    values_cap = vb_in if values_cap is None else values_cap
+    offsets_cap = n_in + 1 if offsets_cap is None else offsets_cap
+    pad = 64
+    sizes = {"keys": shift + keys_cap + pad, "values": shift + values_cap + pad}
+    osizes = {"ko": offsets_cap + pad, "vo": offsets_cap + pad, "ro": b.n + 1 + pad}
+    pattern = np.uint64(int.from_bytes(bytes([GUARD]) * 8, "little"))
+    if device:
+        bufs = {x: torch.full((s,), GUARD, dtype=torch.uint8, device="cuda") for x, s in sizes.items()}
+        offs = {x: torch.from_numpy(np.full(s, pattern).view(np.int64)).cuda() for x, s in osizes.items()}
+        ptr = {x: y.data_ptr() for x, y in {**bufs, **offs}.items()}
+        torch.cuda.synchronize()
+        sp = torch.cuda.current_stream().cuda_stream
+    else:
+        bufs = {x: np.full(s, GUARD, dtype=np.uint8) for x, s in sizes.items()}
+        offs = {x: np.full(s, pattern) for x, s in osizes.items()}
+        ptr = {x: y.ctypes.data for x, y in {**bufs, **offs}.items()}
+        sp = None
+    tot = [ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()]
+    L = _native.lib()
+    rc = L.pbf_sst_scan(hs, len(tables), *b.args(), vp(ptr["keys"] + shift), keys_cap, vp(ptr["ko"]),
+                        vp(ptr["values"] + shift), values_cap, vp(ptr["vo"]), offsets_cap, ctypes.byref(tot[0]),
+                        ctypes.byref(tot[1]), ctypes.byref(tot[2]), vp(ptr["ro"]), 1 if device else 0, vp(sp or None))
+    msg = L.pbf_last_error().decode() if rc else ""
+    if device:
+        torch.cuda.synchronize()
+        bufs = {x: y.cpu().numpy() for x, y in bufs.items()}
+        offs = {x: y.cpu().numpy().view(np.uint64) for x, y in offs.items()}
+    out = dict(rc=rc, msg=msg, n=tot[0].value, kb=tot[1].value, vb=tot[2].value, shift=shift, pattern=pattern,
+               nranges=b.n, n_in=n_in, kb_in=kb_in, vb_in=vb_in, **bufs, **offs)
+    # nothing at or past a stated capacity (or before a shifted base) is ever written
+    for name, cap in (("keys", keys_cap), ("values", values_cap)):
+        assert (out[name][:shift] == GUARD).all() and (out[name][shift + cap:] == GUARD).all(), name
+    for name, cap in (("ko", offsets_cap), ("vo", offsets_cap), ("ro", b.n + 1)):
+        assert (out[name][cap:] == pattern).all(), name
+    return out
+
+
+def runs_from(out):
+    """[[(key, value)] per range] of a successful scan_call."""
+    n, s = out["n"], out["shift"]
+    ko, vo, ro = out["ko"][:n + 1], out["vo"][:n + 1], out["ro"][:out["nranges"] + 1]
+    assert ko[0] == 0 and vo[0] == 0 and int(ko[-1]) == out["kb"] and int(vo[-1]) == out["vb"]
+    assert ro[0] == 0 and int(ro[-1]) == n
+    kb, vb = out["keys"][s:].tobytes(), out["values"][s:].tobytes()
+    recs = [(kb[int(ko[i]):int(ko[i + 1])], vb[int(vo[i]):int(vo[i + 1])]) for i in range(n)]
+    return [recs[int(ro[q]):int(ro[q + 1])] for q in range(out["nranges"])]
+
+
+COPY_RANGES = [(k(30), k(250)), (k(100), k(100)), (k(240), ""), (k(7), k(3)), ("", k(60))]
+
+
+def test_device_pointer_form_equals_host_form(opened):
+    """Both outputs on device pointers, the byte buffers' bases moved by 0 and by 5 bytes, guard
+    bytes on either side."""
+    tables, rows = three_tables(opened)
+    want = model_runs(rows, COPY_RANGES)
+    host = scan_call(tables, COPY_RANGES)
+    assert host["rc"] == 0 and runs_from(host) == want
+    for shift in (0, 5):
+        dev = scan_call(tables, COPY_RANGES, device=True, shift=shift)
+        assert dev["rc"] == 0, dev["msg"]
+        assert runs_from(dev) == want
+        for x in ("n", "kb", "vb"):
+            assert host[x] == dev[x]
+        n = host["n"]
+        for x, m in (("ko", n + 1), ("vo", n + 1), ("ro", len(COPY_RANGES) + 1)):
+            assert np.array_equal(host[x][:m], dev[x][:m]), x
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
+def test_capacity_one_too_small_is_refused(opened, device):
+    """The keys' and the values' capacity one byte short, and offsets_cap (the one capacity of
+    both offsets arrays) one entry short: PBF_ERR_INVALID, the message names the size needed, the
+    totals are set, no byte of the five outputs is written, and the exact capacities succeed."""
+    tables, rows = three_tables(opened)
+    want = model_runs(rows, COPY_RANGES)
+    flat = [r for run in want for r in run]
+    n, kb, vb = len(flat), sum(len(x) for x, _ in flat), sum(len(v) for _, v in flat)
+    exact = scan_call(tables, COPY_RANGES, kb, vb, n + 1, device=device)
+    assert exact["rc"] == 0 and runs_from(exact) == want and (exact["n"], exact["kb"], exact["vb"]) == (n, kb, vb)
+    short = {"keys_cap": (kb - 1, f"the keys need {kb} bytes"), "values_cap": (vb - 1, f"the values need {vb} bytes"),
+             "offsets_cap": (n, f"needs {n + 1} entries")}
+    for arg, (cap, text) in short.items():
+        caps = dict(keys_cap=kb, values_cap=vb, offsets_cap=n + 1)
+        caps[arg] = cap
+        out = scan_call(tables, COPY_RANGES, device=device, **caps)
+        assert out["rc"] == _native.PBF_ERR_INVALID and text in out["msg"], (arg, out["msg"])
+        assert (out["n"], out["kb"], out["vb"]) == (n, kb, vb)  # the totals, for the retry
+        assert (out["keys"] == GUARD).all() and (out["values"] == GUARD).all()
+        for x in ("ko", "vo", "ro"):
+            assert (out[x] == out["pattern"]).all(), x
+    with pytest.raises(ValueError, match=f"the keys need {kb} bytes"):
+        _native.check(scan_call(tables, COPY_RANGES, keys_cap=0, device=device)["rc"], "pbf_sst_scan")
+
+
+# ------------------------------------------------------------------ sizes
+def test_size_totals(opened):
+    """pbf_sst_scan_size's totals are the model's sums over the windows before de-duplication:
+    never below the run's, and equal to them when the tables are disjoint."""
+    tables, rows = three_tables(opened)
+    out = scan_call(tables, COPY_RANGES)
+    sums = [SM.presum(rows, a, b) for a, b in COPY_RANGES]
+    assert (out["n_in"], out["kb_in"], out["vb_in"]) == tuple(sum(s[i] for s in sums) for i in range(3))
+    assert out["n_in"] > out["n"] and out["kb_in"] > out["kb"] and out["vb_in"] > out["vb"]
+    drows = [rows_of(0, range(0, 300, 3)), rows_of(1, range(1, 300, 3)), rows_of(2, range(2, 300, 3))]
+    dtables = [opened(r, 128) for r in drows]
+    out = scan_call(dtables, COPY_RANGES)
+    assert out["rc"] == 0 and (out["n_in"], out["kb_in"], out["vb_in"]) == (out["n"], out["kb"], out["vb"])
+    assert runs_from(out) == model_runs(drows, COPY_RANGES)
+    # either window array may be left out
+    lo, hi, n, _, _ = size_call(tables, COPY_RANGES)
+    b = _Bounds(COPY_RANGES)
+    hs = (vp * 3)(*[t._h.value for t in tables])
+    z = [ctypes.c_uint64() for _ in range(3)]
+    only = np.zeros_like(hi)
+    for args, want in (((None, vp(only.ctypes.data)), hi), ((vp(only.ctypes.data), None), lo)):
+        _native.check(_native.lib().pbf_sst_scan_size(hs, 3, *b.args(), *args, *[ctypes.byref(x) for x in z]), "size")
+        assert np.array_equal(only, want) and z[0].value == n
+
+
+# ------------------------------------------------------------------ equivalences
+def test_open_scan_is_the_merge_and_gets_agree(opened):
+    """scan_tables(ts, "", "") is merge_tables(ts) byte for byte; t.scan("", "") is t.records();
+    every key of a scanned run answers the same value through lsm_get.get_batch."""
+    tables, rows = three_tables(opened)
+    a, b = scan_tables(tables, "", ""), merge_tables(tables)
+    assert a.n == b.n and a.keys.data.tobytes() == b.keys.data.tobytes()
+    assert np.asarray(a.values).tobytes() == np.asarray(b.values).tobytes()
+    assert np.array_equal(a.keys.offsets, b.keys.offsets) and np.array_equal(a.value_offsets, b.value_offsets)
+    for t in tables:
+        assert records_of(t.scan("", "")) == records_of(t.records())
+    run = records_of(scan_tables(tables, k(40), k(260)))
+    table, vals, offs = lsm_get.get_batch([x.decode() for x, _ in run], tables, [])
+    raw = vals.tobytes()
+    assert (table >= 0).all()
+    assert [raw[int(offs[i]):int(offs[i + 1])] for i in range(len(run))] == [v for _, v in run]
+    want = {x: t for x, _, t in SM.scan(rows, k(40), k(260))}
+    assert [int(t) for t in table] == [want[x] for x, _ in run]
+
+
+# ------------------------------------------------------------------ argument refusals
+def test_argument_refusals(opened):
+    a, b = opened(rows_of(0, range(10)), 64), opened(rows_of(1, range(5, 15)), 64)
+    for fn in (scan_ranges, count_ranges):
+        with pytest.raises(ValueError, match="listed twice"):
+            fn([a, b, a], [("", "")])
+        with pytest.raises(ValueError, match="no tables"):
+            fn([], [("", "")])
+        with pytest.raises(ValueError, match=r"must be a str, got None.*records\(\) / merge_tables"):
+            fn([a, b], [("a", "b"), (None, "b")])
+    with pytest.raises(ValueError, match=r"records\(\) / merge_tables"):
+        scan_tables([a], "a", None)
+    with pytest.raises(ValueError, match=r"records\(\) / merge_tables"):
+        a.scan(None, None)
+    with pytest.raises(ValueError, match="no tables"):
+        scan_tables([], "a", "b")
+    c = DeviceSSTable.from_bytes(build_sstable(["x"], [b"y"], 64)[0])
+    stale = c.handle.value
+    c.close()
+    with pytest.raises(ValueError, match="closed"):
+        scan_tables([a, c], "", "")
+    with pytest.raises(ValueError, match="closed"):
+        c.scan("", "")
+    hs = (vp * 2)(a.handle.value, stale)  # the handle itself, after its close
+    z = ctypes.c_uint64()
+    o = np.zeros(64, dtype=np.uint64)
+    L = _native.lib()
+    bd = _Bounds([("", "")])
+    rc = L.pbf_sst_scan(hs, 2, *bd.args(), vp(o.ctypes.data), 0, vp(o.ctypes.data), vp(o.ctypes.data), 0, vp(o.ctypes.data),
+                        64, ctypes.byref(z), ctypes.byref(z), ctypes.byref(z), vp(o.ctypes.data), 0, None)
+    assert rc == _native.PBF_ERR_INVALID and b"closed" in L.pbf_last_error()
+    rc = L.pbf_sst_scan_size(hs, 2, *bd.args(), None, None, ctypes.byref(z), ctypes.byref(z), ctypes.byref(z))
+    assert rc == _native.PBF_ERR_INVALID and b"closed" in L.pbf_last_error()
+    hs = (vp * 1)(a.handle.value)
+    rc = L.pbf_sst_scan(hs, 1, *bd.args(), vp(o.ctypes.data), 0, vp(o.ctypes.data), vp(o.ctypes.data), 0, vp(o.ctypes.data),
+                        64, ctypes.byref(z), ctypes.byref(z), ctypes.byref(z), None, 0, None)
+    assert rc == _native.PBF_ERR_INVALID and b"null pointer" in L.pbf_last_error()
+    rows = [rows_of(0, range(10)), rows_of(1, range(5, 15))]
+    assert len(check_ranges([a, b], rows, [("", "")])[0]) == 15  # and the live ones still scan
+
+
+def test_tables_on_two_devices_are_refused():
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    f = build_sstable(["x"], [b"y"], 64)[0]
+    a, b = DeviceSSTable.from_bytes(f, device=0), DeviceSSTable.from_bytes(f, device=1)
+    try:
+        with pytest.raises(ValueError, match="share a device"):
+            scan_tables([a, b], "", "")
+    finally:
+        a.close()
+        b.close()
+
+
+# ------------------------------------------------------------------ merges and lookups unaffected
+def test_merges_and_lookups_are_the_same_after_a_scan(opened):
+    tables, rows = three_tables(opened)
+    probes = sorted({x for r in rows for x, _ in r}) + ["", "k", "k00001", "zzz"]
+    before = [[x.tobytes() for x in t.get_many(probes)] for t in tables]
+    merged = records_of(merge_tables(tables))
+    check_ranges(tables, rows, COPY_RANGES)
+    assert records_of(merge_tables(tables)) == merged == [(x, v) for x, v, _ in MM.merge(rows)]
+    assert [[x.tobytes() for x in t.get_many(probes)] for t in tables] == before
