@@ -50,27 +50,47 @@ def _bounds(tables) -> tuple[int, int]:
     return n, nbytes
 
 
-def _run(tables: Sequence, mode: int) -> PackedRecords:
+def _table_list(tables, what: str) -> list:
+    """The tables of one merge or scan (`what`) as a list."""
     tables = list(tables)
     if not tables:
-        raise ValueError("no tables to merge")
+        raise ValueError(f"no tables to {what}")
     if len(tables) > MAX_TABLES:
-        raise ValueError(f"a merge takes at most {MAX_TABLES} tables, got {len(tables)}")
+        raise ValueError(f"a {what} takes at most {MAX_TABLES} tables, got {len(tables)}")
+    return tables
+
+
+class _RunOut:
+    """Host arrays for a record run of at most `n` records, `kbytes` key bytes and `vbytes` value
+    bytes, as ``pbf_sst_merge`` and ``pbf_sst_scan`` fill them."""
+
+    def __init__(self, n: int, kbytes: int, vbytes: int):
+        self.keys = np.empty(kbytes, dtype=np.uint8)
+        self.values = np.empty(vbytes, dtype=np.uint8)
+        self.ko = np.empty(n + 1, dtype=np.uint64)
+        self.vo = np.empty(n + 1, dtype=np.uint64)
+        self.n_out, self.kb, self.vb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+
+    def args(self):
+        """keys_out ... value_bytes_out of either call."""
+        return (_vp(self.keys.ctypes.data) if self.keys.size else None, self.keys.size, _vp(self.ko.ctypes.data),
+                _vp(self.values.ctypes.data) if self.values.size else None, self.values.size, _vp(self.vo.ctypes.data),
+                self.ko.size, ctypes.byref(self.n_out), ctypes.byref(self.kb), ctypes.byref(self.vb))
+
+    def records(self) -> PackedRecords:
+        """The run the call wrote."""
+        m = self.n_out.value
+        pk = PackedKeys(self.keys[:self.kb.value], m, offsets=self.ko[:m + 1])
+        return PackedRecords(pk, self.values[:self.vb.value], self.vo[:m + 1])
+
+
+def _run(tables: Sequence, mode: int) -> PackedRecords:
+    tables = _table_list(tables, "merge")
     hs = _handles(tables)
     n, nbytes = _bounds(tables)
-    keys = np.empty(nbytes, dtype=np.uint8)
-    values = np.empty(nbytes, dtype=np.uint8)
-    ko = np.empty(n + 1, dtype=np.uint64)
-    vo = np.empty(n + 1, dtype=np.uint64)
-    n_out, kb, vb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    rc = _native.lib().pbf_sst_merge(hs, len(tables), mode, _vp(keys.ctypes.data) if nbytes else None, nbytes,
-                                     _vp(ko.ctypes.data), _vp(values.ctypes.data) if nbytes else None, nbytes,
-                                     _vp(vo.ctypes.data), n + 1, ctypes.byref(n_out), ctypes.byref(kb),
-                                     ctypes.byref(vb), 0, None)
-    _native.check(rc, "pbf_sst_merge")
-    m = n_out.value
-    pk = PackedKeys(keys[:kb.value], m, offsets=ko[:m + 1])
-    return PackedRecords(pk, values[:vb.value], vo[:m + 1])
+    out = _RunOut(n, nbytes, nbytes)
+    _native.check(_native.lib().pbf_sst_merge(hs, len(tables), mode, *out.args(), 0, None), "pbf_sst_merge")
+    return out.records()
 
 
 def merge_tables(tables: Sequence) -> PackedRecords:

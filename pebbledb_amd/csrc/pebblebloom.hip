@@ -2446,6 +2446,87 @@ int copy_filter_into(pbf_filter_t* src, pbf_filter_t* dst, bool bounce) {
     return wait_stream(dst);
 }
 
+// ---- SSTable build: what pbf_encode_data_blocks, pbf_build_sstable and pbf_build_sstables share
+// A host block plan, block by block: the records ascend (a block may be empty only where
+// empty_ok) and stay within n, a block's records fit 65536 bytes, and block_out steps by each
+// block's encoded size.  What the plan must cover differs by door and is checked there.
+int check_block_plan(const uint64_t* key_offsets, const uint64_t* value_offsets, uint64_t n, const uint64_t* block_first,
+                     const uint64_t* block_out, uint64_t nblocks, bool empty_ok) {
+    for (uint64_t b = 0; b < nblocks; ++b) {
+        const uint64_t r0 = block_first[b], r1 = block_first[b + 1];
+        if ((empty_ok ? r1 < r0 : r1 <= r0) || r1 > n)  // (> n: before offsets[r1] is read)
+            return fail(PBF_ERR_INVALID, empty_ok ? "block plan not monotonic" : "block plan not increasing");
+        const uint64_t dl = (key_offsets[r1] - key_offsets[r0]) + (value_offsets[r1] - value_offsets[r0]) + 8 * (r1 - r0);
+        if (dl > kMaxBlockData) return fail(PBF_ERR_INVALID, "a block's records exceed 65536 bytes");
+        if (block_out[b + 1] - block_out[b] != dl + 2 * (r1 - r0) + 2)
+            return fail(PBF_ERR_INVALID, "block_out does not match the blocks' encoded sizes");
+    }
+    return PBF_OK;
+}
+
+// Large host spans page-locked for the duration of a call, so that their copies are direct DMA
+// (pageable copies go through the runtime's staging at a fraction of the rate); spans that are
+// already pinned, or cannot be registered, are copied as they are.
+struct HostPins {
+    std::vector<void*> registered;
+    void pin(const void* p, uint64_t bytes) {
+        if (bytes < (uint64_t(4) << 20) || is_pinned_host(p)) return;
+        if (hipHostRegister(const_cast<void*>(p), bytes, hipHostRegisterDefault) == hipSuccess)
+            registered.push_back(const_cast<void*>(p));
+        else
+            (void)hipGetLastError();
+    }
+    ~HostPins() {
+        for (void* p : registered) (void)hipHostUnregister(p);
+    }
+};
+struct HostSpan {
+    const void* p;
+    uint64_t bytes;
+};
+
+// One H2D of the first w records of a packed run into f's leased scratch set, and one
+// k_encode_blocks launch over the whole plan into sc->ssec (its error word: sc->serr), all on
+// f's stream.  The inputs and then `outs`, the caller's output spans, are pinned first.  *run =
+// the keys on the device: the data blocks and every filter are built from this one upload.
+int upload_and_encode(pbf_filter_t* f, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
+                      const uint64_t* value_offsets, uint64_t w, const uint64_t* block_first, const uint64_t* block_out,
+                      uint64_t nblocks, HostPins& pins, const std::vector<HostSpan>& outs, Batch* run) {
+    HIP_TRY(allow_lds(k_encode_blocks, kEncodeLds));
+    Scratch* sc = f->sc;
+    hipStream_t s = f->stream;
+    const uint64_t kb = key_offsets[w], vb = value_offsets[w];
+    HIP_TRY(sc->dkeys.ensure(((kb + 15) & ~uint64_t(15)) + 32));
+    HIP_TRY(sc->doffs.ensure((w + 1) * 8));
+    HIP_TRY(sc->svals.ensure(((vb + 15) & ~uint64_t(15)) + 32 + (w + 1) * 8));
+    HIP_TRY(sc->splan.ensure(2 * (nblocks + 1) * 8));
+    HIP_TRY(sc->ssec.ensure(block_out[nblocks] + 32));
+    HIP_TRY(sc->serr.ensure(4));
+    auto* dk = static_cast<uint8_t*>(sc->dkeys.p);
+    auto* dko = static_cast<uint64_t*>(sc->doffs.p);
+    auto* dv = static_cast<uint8_t*>(sc->svals.p);
+    auto* dvo = reinterpret_cast<uint64_t*>(dv + ((vb + 15) & ~uint64_t(15)) + 32);
+    auto* dbf = static_cast<uint64_t*>(sc->splan.p);
+    auto* dbo = dbf + nblocks + 1;
+    pins.pin(keys, kb);
+    pins.pin(values, vb);
+    pins.pin(key_offsets, (w + 1) * 8);
+    pins.pin(value_offsets, (w + 1) * 8);
+    for (const HostSpan& o : outs) pins.pin(o.p, o.bytes);
+    if (kb) HIP_TRY(hipMemcpyAsync(dk, keys, kb, hipMemcpyHostToDevice, s));
+    if (vb) HIP_TRY(hipMemcpyAsync(dv, values, vb, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dko, key_offsets, (w + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dvo, value_offsets, (w + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dbf, block_first, (nblocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dbo, block_out, (nblocks + 1) * 8, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(sc->serr.p, 0, 4, s));
+    k_encode_blocks<<<uint32_t(nblocks), 512, kEncodeLds, s>>>(dk, dko, dv, dvo, dbf, dbo, static_cast<uint8_t*>(sc->ssec.p),
+                                                               static_cast<unsigned int*>(sc->serr.p));
+    LAUNCHED(f, "k_encode_blocks");
+    *run = make_batch(dk, dko, 0, w);
+    return PBF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -3095,14 +3176,8 @@ int pbf_encode_data_blocks(int device, const uint8_t* keys, const uint64_t* key_
         // the host plan is checked here: blocks cover records 0..n in order, each fits a block
         if (block_first[0] != 0 || block_first[nblocks] != n || block_out[0] != 0)
             return fail(PBF_ERR_INVALID, "block plan must cover records [0, n) from byte 0");
-        for (uint64_t b = 0; b < nblocks; ++b) {
-            const uint64_t r0 = block_first[b], r1 = block_first[b + 1];
-            if (r1 < r0 || r1 > n) return fail(PBF_ERR_INVALID, "block plan not monotonic");  // (> n: before offsets[r1] is read)
-            const uint64_t dl = (key_offsets[r1] - key_offsets[r0]) + (value_offsets[r1] - value_offsets[r0]) + 8 * (r1 - r0);
-            if (dl > kMaxBlockData) return fail(PBF_ERR_INVALID, "a block's records exceed 65536 bytes");
-            if (block_out[b + 1] - block_out[b] != dl + 2 * (r1 - r0) + 2)
-                return fail(PBF_ERR_INVALID, "block_out does not match the blocks' encoded sizes");
-        }
+        int rc = check_block_plan(key_offsets, value_offsets, n, block_first, block_out, nblocks, true);
+        if (rc) return rc;
         out_bytes = block_out[nblocks];
         const uint64_t kb = key_offsets[n], vb = value_offsets[n];
         HIP_TRY(c.keys.ensure(kb + 16));
@@ -3153,66 +3228,18 @@ int pbf_build_sstable(pbf_filter_t* f, const uint8_t* keys, const uint64_t* key_
     // the host plan is checked as in pbf_encode_data_blocks
     if (block_first[0] != 0 || block_first[nblocks] != n || block_out[0] != 0)
         return fail(PBF_ERR_INVALID, "block plan must cover records [0, n) from byte 0");
-    for (uint64_t b = 0; b < nblocks; ++b) {
-        const uint64_t r0 = block_first[b], r1 = block_first[b + 1];
-        if (r1 < r0 || r1 > n) return fail(PBF_ERR_INVALID, "block plan not monotonic");  // (> n: before offsets[r1] is read)
-        const uint64_t dl = (key_offsets[r1] - key_offsets[r0]) + (value_offsets[r1] - value_offsets[r0]) + 8 * (r1 - r0);
-        if (dl > kMaxBlockData) return fail(PBF_ERR_INVALID, "a block's records exceed 65536 bytes");
-        if (block_out[b + 1] - block_out[b] != dl + 2 * (r1 - r0) + 2)
-            return fail(PBF_ERR_INVALID, "block_out does not match the blocks' encoded sizes");
-    }
-    HIP_TRY(allow_lds(k_encode_blocks, kEncodeLds));
+    if ((rc = check_block_plan(key_offsets, value_offsets, n, block_first, block_out, nblocks, true))) return rc;
     LEASE(f);
     Scratch* sc = f->sc;
     hipStream_t s = f->stream;
-    const uint64_t kb = key_offsets[n], vb = value_offsets[n], out_bytes = block_out[nblocks];
-    HIP_TRY(sc->dkeys.ensure(((kb + 15) & ~uint64_t(15)) + 32));
-    HIP_TRY(sc->doffs.ensure((n + 1) * 8));
-    HIP_TRY(sc->svals.ensure(((vb + 15) & ~uint64_t(15)) + 32 + (n + 1) * 8));
-    HIP_TRY(sc->splan.ensure(2 * (nblocks + 1) * 8));
-    HIP_TRY(sc->ssec.ensure(out_bytes + 32));
-    HIP_TRY(sc->serr.ensure(4));
-    auto* dk = static_cast<uint8_t*>(sc->dkeys.p);
-    auto* dko = static_cast<uint64_t*>(sc->doffs.p);
-    auto* dv = static_cast<uint8_t*>(sc->svals.p);
-    auto* dvo = reinterpret_cast<uint64_t*>(dv + ((vb + 15) & ~uint64_t(15)) + 32);
-    auto* dbf = static_cast<uint64_t*>(sc->splan.p);
-    auto* dbo = dbf + nblocks + 1;
-    // Page-lock the large host spans for the duration of the call so the copies are direct DMA
-    // (pageable copies go through the runtime's staging at a fraction of the rate); spans that
-    // are already pinned, or cannot be registered, are copied as they are.
-    std::vector<void*> registered;
-    auto lock_span = [&](const void* p, uint64_t bytes) {
-        if (bytes < (uint64_t(4) << 20) || is_pinned_host(p)) return;
-        if (hipHostRegister(const_cast<void*>(p), bytes, hipHostRegisterDefault) == hipSuccess)
-            registered.push_back(const_cast<void*>(p));
-        else
-            (void)hipGetLastError();
-    };
-    struct Unregister {
-        std::vector<void*>& v;
-        ~Unregister() {
-            for (void* p : v) (void)hipHostUnregister(p);
-        }
-    } unreg{registered};
-    lock_span(keys, kb);
-    lock_span(values, vb);
-    lock_span(key_offsets, (n + 1) * 8);
-    lock_span(value_offsets, (n + 1) * 8);
-    lock_span(data_out, out_bytes);
-    // one H2D of the packed records; the data blocks and the filter are both built from it
-    if (kb) HIP_TRY(hipMemcpyAsync(dk, keys, kb, hipMemcpyHostToDevice, s));
-    if (vb) HIP_TRY(hipMemcpyAsync(dv, values, vb, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dko, key_offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dvo, value_offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dbf, block_first, (nblocks + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(dbo, block_out, (nblocks + 1) * 8, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemsetAsync(sc->serr.p, 0, 4, s));
-    k_encode_blocks<<<uint32_t(nblocks), 512, kEncodeLds, s>>>(dk, dko, dv, dvo, dbf, dbo, static_cast<uint8_t*>(sc->ssec.p),
-                                                               static_cast<unsigned int*>(sc->serr.p));
-    LAUNCHED(f, "k_encode_blocks");
+    const uint64_t out_bytes = block_out[nblocks];
+    HostPins pins;
+    Batch run;
+    rc = upload_and_encode(f, keys, key_offsets, values, value_offsets, n, block_first, block_out, nblocks, pins,
+                           {{data_out, out_bytes}}, &run);
+    if (rc) return rc;
     if (f->k > 0) {  // SSTableBuilder.build's filter over every key (sstable.py:274)
-        rc = add_device(f, make_batch(dk, dko, 0, n));
+        rc = add_device(f, run);
         if (rc) return rc;
     }
     unsigned int err = 0;
@@ -3254,14 +3281,8 @@ int pbf_build_sstables(pbf_filter_t* const* filters, uint32_t ntables, const uin
     if (table_blocks[0] != 0 || table_blocks[ntables] != nblocks) return fail(PBF_ERR_INVALID, "tables must cover the blocks");
     for (uint32_t t = 0; t < ntables; ++t)
         if (table_blocks[t + 1] <= table_blocks[t]) return fail(PBF_ERR_INVALID, "a table without blocks");
-    for (uint64_t b = 0; b < nblocks; ++b) {
-        const uint64_t r0 = block_first[b], r1 = block_first[b + 1];
-        if (r1 <= r0 || r1 > n) return fail(PBF_ERR_INVALID, "block plan not increasing");  // (> n: before offsets[r1] is read)
-        const uint64_t dl = (key_offsets[r1] - key_offsets[r0]) + (value_offsets[r1] - value_offsets[r0]) + 8 * (r1 - r0);
-        if (dl > kMaxBlockData) return fail(PBF_ERR_INVALID, "a block's records exceed 65536 bytes");
-        if (block_out[b + 1] - block_out[b] != dl + 2 * (r1 - r0) + 2)
-            return fail(PBF_ERR_INVALID, "block_out does not match the blocks' encoded sizes");
-    }
+    int rc = check_block_plan(key_offsets, value_offsets, n, block_first, block_out, nblocks, false);
+    if (rc) return rc;
     const uint64_t w = block_first[nblocks];  // records written (the run's tail may be left out)
     // every handle of the set, in address order
     std::vector<pbf_filter_t*> order(filters, filters + ntables);
@@ -3270,59 +3291,21 @@ int pbf_build_sstables(pbf_filter_t* const* filters, uint32_t ntables, const uin
     locks.reserve(ntables);
     for (pbf_filter_t* p : order) locks.emplace_back(p->mu);
     pbf_filter_t* f0 = filters[0];
-    int rc = enter(f0);
-    if (rc) return rc;
-    HIP_TRY(allow_lds(k_encode_blocks, kEncodeLds));
+    if ((rc = enter(f0))) return rc;
     LEASE(f0);
     Scratch* sc = f0->sc;
     hipStream_t s0 = f0->stream;
-    const uint64_t kb = key_offsets[w], vb = value_offsets[w], out_bytes = block_out[nblocks];
-    HIP_TRY(sc->dkeys.ensure(((kb + 15) & ~uint64_t(15)) + 32));
-    HIP_TRY(sc->doffs.ensure((w + 1) * 8));
-    HIP_TRY(sc->svals.ensure(((vb + 15) & ~uint64_t(15)) + 32 + (w + 1) * 8));
-    HIP_TRY(sc->splan.ensure(2 * (nblocks + 1) * 8));
-    HIP_TRY(sc->ssec.ensure(out_bytes + 32));
-    HIP_TRY(sc->serr.ensure(4));
-    auto* dk = static_cast<uint8_t*>(sc->dkeys.p);
-    auto* dko = static_cast<uint64_t*>(sc->doffs.p);
-    auto* dv = static_cast<uint8_t*>(sc->svals.p);
-    auto* dvo = reinterpret_cast<uint64_t*>(dv + ((vb + 15) & ~uint64_t(15)) + 32);
-    auto* dbf = static_cast<uint64_t*>(sc->splan.p);
-    auto* dbo = dbf + nblocks + 1;
-    auto* dsec = static_cast<uint8_t*>(sc->ssec.p);
-    std::vector<void*> registered;
-    auto lock_span = [&](const void* p, uint64_t bytes) {
-        if (bytes < (uint64_t(4) << 20) || is_pinned_host(p)) return;
-        if (hipHostRegister(const_cast<void*>(p), bytes, hipHostRegisterDefault) == hipSuccess)
-            registered.push_back(const_cast<void*>(p));
-        else
-            (void)hipGetLastError();
-    };
-    struct Unregister {
-        std::vector<void*>& v;
-        ~Unregister() {
-            for (void* p : v) (void)hipHostUnregister(p);
-        }
-    } unreg{registered};
-    lock_span(keys, kb);
-    lock_span(values, vb);
-    lock_span(key_offsets, (w + 1) * 8);
-    lock_span(value_offsets, (w + 1) * 8);
+    std::vector<HostSpan> outs;
     for (uint32_t t = 0; t < ntables; ++t) {
-        lock_span(data_outs[t], block_out[table_blocks[t + 1]] - block_out[table_blocks[t]]);
-        if (bitmap_outs && bitmap_outs[t]) lock_span(bitmap_outs[t], filters[t]->nb_bytes);
+        outs.push_back({data_outs[t], block_out[table_blocks[t + 1]] - block_out[table_blocks[t]]});
+        if (bitmap_outs && bitmap_outs[t]) outs.push_back({bitmap_outs[t], filters[t]->nb_bytes});
     }
-    // one H2D of the run; the data blocks of every output and every filter are built from it
-    if (kb) HIP_TRY(hipMemcpyAsync(dk, keys, kb, hipMemcpyHostToDevice, s0));
-    if (vb) HIP_TRY(hipMemcpyAsync(dv, values, vb, hipMemcpyHostToDevice, s0));
-    HIP_TRY(hipMemcpyAsync(dko, key_offsets, (w + 1) * 8, hipMemcpyHostToDevice, s0));
-    HIP_TRY(hipMemcpyAsync(dvo, value_offsets, (w + 1) * 8, hipMemcpyHostToDevice, s0));
-    HIP_TRY(hipMemcpyAsync(dbf, block_first, (nblocks + 1) * 8, hipMemcpyHostToDevice, s0));
-    HIP_TRY(hipMemcpyAsync(dbo, block_out, (nblocks + 1) * 8, hipMemcpyHostToDevice, s0));
-    HIP_TRY(hipMemsetAsync(sc->serr.p, 0, 4, s0));
-    k_encode_blocks<<<uint32_t(nblocks), 512, kEncodeLds, s0>>>(dk, dko, dv, dvo, dbf, dbo, dsec,
-                                                                static_cast<unsigned int*>(sc->serr.p));
-    LAUNCHED(f0, "k_encode_blocks");
+    HostPins pins;
+    Batch all;
+    rc = upload_and_encode(f0, keys, key_offsets, values, value_offsets, w, block_first, block_out, nblocks, pins, outs,
+                           &all);
+    if (rc) return rc;
+    auto* dsec = static_cast<const uint8_t*>(sc->ssec.p);
     HIP_TRY(filter_event(f0));
     HIP_TRY(hipEventRecord(f0->ev, s0));  // the run is on the device
     // the data sections go back on s0 while the filters build on their own streams
@@ -3330,7 +3313,6 @@ int pbf_build_sstables(pbf_filter_t* const* filters, uint32_t ntables, const uin
         const uint64_t o0 = block_out[table_blocks[t]], o1 = block_out[table_blocks[t + 1]];
         HIP_TRY(hipMemcpyAsync(data_outs[t], dsec + o0, o1 - o0, hipMemcpyDeviceToHost, s0));
     }
-    const Batch all = make_batch(dk, dko, 0, w);
     for (uint32_t t = 0; t < ntables; ++t) {
         pbf_filter_t* ft = filters[t];
         const uint64_t r0 = block_first[table_blocks[t]], r1 = block_first[table_blocks[t + 1]];
@@ -3637,6 +3619,19 @@ int sst_ctx_stream(SstCtx& c, int device) {
     return PBF_OK;
 }
 
+// offsets[n+1] = the exclusive scan of max(len[i], 0), closed by the total, for n > 0: the
+// three-launch scan of sstable_read_kernels.hpp on `s`.  sums = one word of scratch per tile.
+int len_scan(const int32_t* len, uint64_t n, uint64_t* sums, uint64_t* offsets, hipStream_t s) {
+    const uint64_t ntiles = (n + kScanTile - 1) / kScanTile;
+    k_len_tile_sums<<<uint32_t(ntiles), kScanThreads, 0, s>>>(len, n, sums);
+    CHECK_LAUNCH();
+    k_len_tile_scan<<<1, kScanThreads, 0, s>>>(sums, ntiles);
+    CHECK_LAUNCH();
+    k_len_offsets<<<uint32_t(ntiles), kScanThreads, 0, s>>>(len, n, sums, offsets);
+    CHECK_LAUNCH();
+    return PBF_OK;
+}
+
 // The tables of one call, each locked shared (once, however often it is named).
 struct SstLocks {
     std::vector<pbf_sstable_t*> held;
@@ -3929,13 +3924,7 @@ int pbf_sst_gather(pbf_sstable_t* const* tables, uint32_t ntables, const int32_t
         const uint64_t ntiles = (n + kScanTile - 1) / kScanTile;
         if (ntiles > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "batch too large");
         HIP_TRY(c.tmp.ensure(ntiles * 8));
-        auto* sums = static_cast<uint64_t*>(c.tmp.p);
-        k_len_tile_sums<<<uint32_t(ntiles), kScanThreads, 0, s>>>(dvl, n, sums);
-        CHECK_LAUNCH();
-        k_len_tile_scan<<<1, kScanThreads, 0, s>>>(sums, ntiles);
-        CHECK_LAUNCH();
-        k_len_offsets<<<uint32_t(ntiles), kScanThreads, 0, s>>>(dvl, n, sums, doffs);
-        CHECK_LAUNCH();
+        if ((rc = len_scan(dvl, n, static_cast<uint64_t*>(c.tmp.p), doffs, s))) return rc;
     }
     uint64_t total = 0;
     HIP_TRY(hipMemcpyAsync(&total, doffs + n, 8, hipMemcpyDeviceToHost, s));
@@ -4002,38 +3991,26 @@ int sst_rec_base(pbf_sstable_t* t) {
     return PBF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint8_t* keys_out, uint64_t keys_cap,
-                  uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
-                  uint64_t offsets_cap, uint64_t* n_out, uint64_t* key_bytes_out, uint64_t* value_bytes_out,
-                  int on_device, void* stream) {
+// The table list of a merge or a scan (`what`), before any lock is taken.
+int check_run_tables(pbf_sstable_t* const* tables, uint32_t ntables, const char* what) {
     if (!tables || ntables == 0) return fail(PBF_ERR_INVALID, "no tables");
     if (ntables > kSstTablesPerLaunch)
-        return fail(PBF_ERR_INVALID, "a merge takes at most " + std::to_string(kSstTablesPerLaunch) + " tables, got " +
-                                         std::to_string(ntables));
-    if (mode != PBF_MERGE_DEDUP && mode != PBF_MERGE_CONCAT) return fail(PBF_ERR_INVALID, "unknown merge mode");
-    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out)
-        return fail(PBF_ERR_INVALID, "null pointer");
-    {
-        std::vector<pbf_sstable_t*> u(tables, tables + ntables);
-        std::sort(u.begin(), u.end());
-        if (std::adjacent_find(u.begin(), u.end()) != u.end())
-            return fail(PBF_ERR_INVALID, "the same table is listed twice");
-    }
-    SstLocks locks;
-    int rc = locks.take(tables, ntables);
-    if (rc) return rc;
-    const int device = tables[0]->device;
-    HIP_TRY(hipSetDevice(device));
-    MergeSet set{};
+        return fail(PBF_ERR_INVALID, std::string("a ") + what + " takes at most " + std::to_string(kSstTablesPerLaunch) +
+                                         " tables, got " + std::to_string(ntables));
+    std::vector<pbf_sstable_t*> u(tables, tables + ntables);
+    std::sort(u.begin(), u.end());
+    if (std::adjacent_find(u.begin(), u.end()) != u.end()) return fail(PBF_ERR_INVALID, "the same table is listed twice");
+    return PBF_OK;
+}
+
+// The locked tables as the kernels take them; *nrec = their records together.
+int fill_merge_set(pbf_sstable_t* const* tables, uint32_t ntables, MergeSet& set, uint64_t* nrec) {
     set.nt = ntables;
     uint64_t n = 0;
     for (uint32_t t = 0; t < ntables; ++t) {
         pbf_sstable_t* tb = tables[t];
-        if ((rc = sst_rec_base(tb))) return rc;
+        int rc = sst_rec_base(tb);
+        if (rc) return rc;
         set.data[t] = static_cast<const uint8_t*>(tb->data.p);
         set.index[t] = static_cast<const SstBlock*>(tb->index.p);
         set.last_prefix[t] = static_cast<const uint64_t*>(tb->prefix.p);
@@ -4042,48 +4019,85 @@ int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint
         set.in_base[t] = n;
         n += tb->nrecords;
     }
-    const uint64_t ntiles = (n + kScanTile - 1) / kScanTile;
-    if (n == 0 || ntiles > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "run too large");
-    SstCtx& c = sst_ctx(device);
-    std::lock_guard<std::mutex> lock(c.mu);
-    rc = sst_ctx_stream(c, device);
-    if (rc) return rc;
-    if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
-    hipStream_t s = on_device ? static_cast<hipStream_t>(stream) : c.stream;
+    *nrec = n;
+    return PBF_OK;
+}
+
+// Where a call wants its record run: in host memory (staged through the context, on its stream)
+// or, on_device, in the caller's device buffers on the caller's stream.
+struct RunOut {
+    uint8_t* keys;
+    uint64_t keys_cap;
+    uint64_t* key_offsets;
+    uint8_t* values;
+    uint64_t values_cap;
+    uint64_t* value_offsets;
+    uint64_t offsets_cap;
+    uint64_t *n, *key_bytes, *value_bytes;  // the run's totals, written even where it does not fit
+    int on_device;
+    hipStream_t s;
+};
+
+// The context's working memory for a run over n ranked input records.
+struct RunWork {
+    uint64_t n = 0, ntiles = 0;
+    MergeSlot* slots = nullptr;
+    uint64_t *pos = nullptr, *sums = nullptr, *totals = nullptr;
+};
+
+// Sizes the working memory for n input records and zeroes the slots on o.s; the caller's rank
+// kernel fills them next.  n == 0 needs none.  The caller holds c.mu and has waited for
+// merge_done, as for everything below.
+int run_prepare(SstCtx& c, const RunOut& o, uint64_t n, RunWork& w) {
+    w.n = n;
+    w.ntiles = (n + kScanTile - 1) / kScanTile;
+    if (w.ntiles > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "run too large");
+    if (n == 0) return PBF_OK;
     HIP_TRY(c.mslots.ensure(n * sizeof(MergeSlot)));
     HIP_TRY(c.mpos.ensure(n * 8));
-    HIP_TRY(c.msums.ensure((kMergeTotals * ntiles + kMergeTotals) * 8));
-    auto* slots = static_cast<MergeSlot*>(c.mslots.p);
-    auto* pos = static_cast<uint64_t*>(c.mpos.p);
-    auto* sums = static_cast<uint64_t*>(c.msums.p);
-    uint64_t* totals = sums + kMergeTotals * ntiles;
+    HIP_TRY(c.msums.ensure((kMergeTotals * w.ntiles + kMergeTotals) * 8));
+    w.slots = static_cast<MergeSlot*>(c.mslots.p);
+    w.pos = static_cast<uint64_t*>(c.mpos.p);
+    w.sums = static_cast<uint64_t*>(c.msums.p);
+    w.totals = w.sums + kMergeTotals * w.ntiles;
     // (a slot no record claims stays dropped: the ranks are a permutation, this is the belt)
-    HIP_TRY(hipMemsetAsync(slots, 0, n * sizeof(MergeSlot), s));
-    k_merge_rank<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(set, n, mode == PBF_MERGE_DEDUP, slots);
-    CHECK_LAUNCH();
-    k_merge_tile_sums<<<uint32_t(ntiles), kScanThreads, 0, s>>>(slots, n, sums, ntiles);
-    CHECK_LAUNCH();
-    k_merge_tile_scan<<<1, kScanThreads, 0, s>>>(sums, ntiles, totals);
-    CHECK_LAUNCH();
+    HIP_TRY(hipMemsetAsync(w.slots, 0, n * sizeof(MergeSlot), o.s));
+    return PBF_OK;
+}
+
+// From the ranked slots to the end of the call: the totals (one sync; reported before any
+// refusal, for the retry), the capacities, the offsets and the bytes of the run.  `extra()`
+// queues what else the door wants on o.s once the run is queued, while the working memory is
+// still its own.  Then the device form records merge_done and the tables' use; the host form
+// copies the run back and waits.  An empty run (n == 0) is the two offsets arrays {0}.
+template <class Extra>
+int run_emit(SstCtx& c, SstLocks& locks, const MergeSet& set, const RunWork& w, const RunOut& o, Extra extra) {
+    hipStream_t s = o.s;
     uint64_t tot[kMergeTotals] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(tot, totals, sizeof tot, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *n_out = tot[0];
-    *key_bytes_out = tot[1];
-    *value_bytes_out = tot[2];
-    if (tot[0] + 1 > offsets_cap)
+    if (w.n) {
+        k_merge_tile_sums<<<uint32_t(w.ntiles), kScanThreads, 0, s>>>(w.slots, w.n, w.sums, w.ntiles);
+        CHECK_LAUNCH();
+        k_merge_tile_scan<<<1, kScanThreads, 0, s>>>(w.sums, w.ntiles, w.totals);
+        CHECK_LAUNCH();
+        HIP_TRY(hipMemcpyAsync(tot, w.totals, sizeof tot, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    *o.n = tot[0];
+    *o.key_bytes = tot[1];
+    *o.value_bytes = tot[2];
+    if (tot[0] + 1 > o.offsets_cap)
         return fail(PBF_ERR_INVALID, "the run holds " + std::to_string(tot[0]) + " records: each offsets array needs " +
                                          std::to_string(tot[0] + 1) + " entries, offsets_cap is " +
-                                         std::to_string(offsets_cap));
-    if (tot[1] > keys_cap || (tot[1] && !keys_out))
+                                         std::to_string(o.offsets_cap));
+    if (tot[1] > o.keys_cap || (tot[1] && !o.keys))
         return fail(PBF_ERR_INVALID, "the keys need " + std::to_string(tot[1]) + " bytes, keys_out holds " +
-                                         std::to_string(keys_out ? keys_cap : 0));
-    if (tot[2] > values_cap || (tot[2] && !values_out))
+                                         std::to_string(o.keys ? o.keys_cap : 0));
+    if (tot[2] > o.values_cap || (tot[2] && !o.values))
         return fail(PBF_ERR_INVALID, "the values need " + std::to_string(tot[2]) + " bytes, values_out holds " +
-                                         std::to_string(values_out ? values_cap : 0));
-    uint8_t *dk = keys_out, *dv = values_out;
-    uint64_t *dko = key_offsets_out, *dvo = value_offsets_out;
-    if (!on_device) {
+                                         std::to_string(o.values ? o.values_cap : 0));
+    uint8_t *dk = o.keys, *dv = o.values;
+    uint64_t *dko = o.key_offsets, *dvo = o.value_offsets;
+    if (!o.on_device) {
         HIP_TRY(c.mkeys.ensure(tot[1] + 16));
         HIP_TRY(c.mvals.ensure(tot[2] + 16));
         HIP_TRY(c.mko.ensure((tot[0] + 1) * 8));
@@ -4093,21 +4107,64 @@ int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint
         dko = static_cast<uint64_t*>(c.mko.p);
         dvo = static_cast<uint64_t*>(c.mvo.p);
     }
-    k_merge_offsets<<<uint32_t(ntiles), kScanThreads, 0, s>>>(slots, n, sums, ntiles, pos, dko, dvo);
-    CHECK_LAUNCH();
-    k_merge_copy<<<grid_for(n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(set, slots, n, pos, totals, dko, dvo, dk, dv);
-    CHECK_LAUNCH();
-    if (on_device) {
+    if (w.n) {
+        k_merge_offsets<<<uint32_t(w.ntiles), kScanThreads, 0, s>>>(w.slots, w.n, w.sums, w.ntiles, w.pos, dko, dvo);
+        CHECK_LAUNCH();
+        k_merge_copy<<<grid_for(w.n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(set, w.slots, w.n, w.pos, w.totals, dko,
+                                                                                 dvo, dk, dv);
+        CHECK_LAUNCH();
+    } else {
+        HIP_TRY(hipMemsetAsync(dko, 0, 8, s));
+        HIP_TRY(hipMemsetAsync(dvo, 0, 8, s));
+    }
+    int rc = extra();
+    if (rc) return rc;
+    if (o.on_device) {
         if (!c.merge_done) HIP_TRY(hipEventCreateWithFlags(&c.merge_done, hipEventDisableTiming));
         HIP_TRY(hipEventRecord(c.merge_done, s));
         return locks.used_on(s);
     }
-    HIP_TRY(hipMemcpyAsync(key_offsets_out, dko, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(value_offsets_out, dvo, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (tot[1]) HIP_TRY(hipMemcpyAsync(keys_out, dk, tot[1], hipMemcpyDeviceToHost, s));
-    if (tot[2]) HIP_TRY(hipMemcpyAsync(values_out, dv, tot[2], hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o.key_offsets, dko, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(o.value_offsets, dvo, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (tot[1]) HIP_TRY(hipMemcpyAsync(o.keys, dk, tot[1], hipMemcpyDeviceToHost, s));
+    if (tot[2]) HIP_TRY(hipMemcpyAsync(o.values, dv, tot[2], hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return PBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint8_t* keys_out, uint64_t keys_cap,
+                  uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
+                  uint64_t offsets_cap, uint64_t* n_out, uint64_t* key_bytes_out, uint64_t* value_bytes_out,
+                  int on_device, void* stream) {
+    int rc = check_run_tables(tables, ntables, "merge");
+    if (rc) return rc;
+    if (mode != PBF_MERGE_DEDUP && mode != PBF_MERGE_CONCAT) return fail(PBF_ERR_INVALID, "unknown merge mode");
+    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out)
+        return fail(PBF_ERR_INVALID, "null pointer");
+    SstLocks locks;
+    if ((rc = locks.take(tables, ntables))) return rc;
+    const int device = tables[0]->device;
+    HIP_TRY(hipSetDevice(device));
+    MergeSet set{};
+    uint64_t n = 0;
+    if ((rc = fill_merge_set(tables, ntables, set, &n))) return rc;
+    if (n == 0) return fail(PBF_ERR_INVALID, "run too large");
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    if ((rc = sst_ctx_stream(c, device))) return rc;
+    if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
+    hipStream_t s = on_device ? static_cast<hipStream_t>(stream) : c.stream;
+    const RunOut o{keys_out, keys_cap, key_offsets_out, values_out, values_cap, value_offsets_out, offsets_cap,
+                   n_out, key_bytes_out, value_bytes_out, on_device, s};
+    RunWork w;
+    if ((rc = run_prepare(c, o, n, w))) return rc;
+    k_merge_rank<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(set, n, mode == PBF_MERGE_DEDUP, w.slots);
+    CHECK_LAUNCH();
+    return run_emit(c, locks, set, w, o, [] { return int(PBF_OK); });
 }
 
 }  // extern "C"
@@ -4138,13 +4195,8 @@ size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 
 // The checks that need no device: the table list and the ranges.
 int scan_check(pbf_sstable_t* const* tables, uint32_t ntables, const ScanArgs& a) {
-    if (!tables || ntables == 0) return fail(PBF_ERR_INVALID, "no tables");
-    if (ntables > kSstTablesPerLaunch)
-        return fail(PBF_ERR_INVALID, "a scan takes at most " + std::to_string(kSstTablesPerLaunch) + " tables, got " +
-                                         std::to_string(ntables));
-    std::vector<pbf_sstable_t*> u(tables, tables + ntables);
-    std::sort(u.begin(), u.end());
-    if (std::adjacent_find(u.begin(), u.end()) != u.end()) return fail(PBF_ERR_INVALID, "the same table is listed twice");
+    int rc = check_run_tables(tables, ntables, "scan");
+    if (rc) return rc;
     if (a.nranges == 0) return PBF_OK;
     if (a.nranges > kScanMaxSegments / ntables)
         return fail(PBF_ERR_INVALID, "a scan takes at most " + std::to_string(kScanMaxSegments) +
@@ -4167,20 +4219,9 @@ int scan_check(pbf_sstable_t* const* tables, uint32_t ntables, const ScanArgs& a
 // for merge_done.
 int scan_segments(SstCtx& c, hipStream_t s, pbf_sstable_t* const* tables, uint32_t ntables, const ScanArgs& a,
                   ScanSegments& g) {
-    int rc;
-    g.set.nt = ntables;
     uint64_t nrec = 0;
-    for (uint32_t t = 0; t < ntables; ++t) {
-        pbf_sstable_t* tb = tables[t];
-        if ((rc = sst_rec_base(tb))) return rc;
-        g.set.data[t] = static_cast<const uint8_t*>(tb->data.p);
-        g.set.index[t] = static_cast<const SstBlock*>(tb->index.p);
-        g.set.last_prefix[t] = static_cast<const uint64_t*>(tb->prefix.p);
-        g.set.rec_base[t] = static_cast<const uint32_t*>(tb->rec_base.p);
-        g.set.nblocks[t] = tb->nblocks;
-        g.set.in_base[t] = nrec;
-        nrec += tb->nrecords;
-    }
+    int rc = fill_merge_set(tables, ntables, g.set, &nrec);
+    if (rc) return rc;
     const uint64_t Q = a.nranges;
     g.nseg = Q * ntables;
     g.n = 0;
@@ -4211,13 +4252,7 @@ int scan_segments(SstCtx& c, hipStream_t s, pbf_sstable_t* const* tables, uint32
     k_scan_bounds<<<grid_for(g.nseg, 256, 1u << 20), 256, 0, s>>>(g.set, b, g.nseg, g.seg_lo, g.seg_cnt);
     CHECK_LAUNCH();
     // (a count is below 2^31: the length scan reads it as a non-negative i32)
-    const int32_t* cnt = reinterpret_cast<const int32_t*>(g.seg_cnt);
-    k_len_tile_sums<<<uint32_t(stiles), kScanThreads, 0, s>>>(cnt, g.nseg, sums);
-    CHECK_LAUNCH();
-    k_len_tile_scan<<<1, kScanThreads, 0, s>>>(sums, stiles);
-    CHECK_LAUNCH();
-    k_len_offsets<<<uint32_t(stiles), kScanThreads, 0, s>>>(cnt, g.nseg, sums, g.seg_base);
-    CHECK_LAUNCH();
+    if ((rc = len_scan(reinterpret_cast<const int32_t*>(g.seg_cnt), g.nseg, sums, g.seg_base, s))) return rc;
     HIP_TRY(hipMemcpyAsync(&g.n, g.seg_base + g.nseg, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return PBF_OK;
@@ -4295,83 +4330,32 @@ int pbf_sst_scan(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* 
     hipStream_t s = on_device ? static_cast<hipStream_t>(stream) : c.stream;
     ScanSegments g;
     if ((rc = scan_segments(c, s, tables, ntables, a, g))) return rc;
-    const uint64_t n = g.n, ntiles = (n + kScanTile - 1) / kScanTile;
-    if (ntiles > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "run too large");
-    MergeSlot* slots = nullptr;
-    uint64_t *pos = nullptr, *sums = nullptr, *totals = nullptr;
-    uint64_t tot[kMergeTotals] = {0, 0, 0};
-    if (n) {
-        HIP_TRY(c.mslots.ensure(n * sizeof(MergeSlot)));
-        HIP_TRY(c.mpos.ensure(n * 8));
-        HIP_TRY(c.msums.ensure((kMergeTotals * ntiles + kMergeTotals) * 8));
-        slots = static_cast<MergeSlot*>(c.mslots.p);
-        pos = static_cast<uint64_t*>(c.mpos.p);
-        sums = static_cast<uint64_t*>(c.msums.p);
-        totals = sums + kMergeTotals * ntiles;
-        // (a slot no record claims stays dropped: the ranks are a permutation, this is the belt)
-        HIP_TRY(hipMemsetAsync(slots, 0, n * sizeof(MergeSlot), s));
-        k_scan_rank<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(g.set, g.seg_base, g.seg_lo, g.seg_cnt, g.nseg, n, slots);
+    const RunOut o{keys_out, keys_cap, key_offsets_out, values_out, values_cap, value_offsets_out, offsets_cap,
+                   n_out, key_bytes_out, value_bytes_out, on_device, s};
+    RunWork w;
+    if ((rc = run_prepare(c, o, g.n, w))) return rc;
+    if (w.n) {
+        k_scan_rank<<<grid_for(w.n, 256, 1u << 20), 256, 0, s>>>(g.set, g.seg_base, g.seg_lo, g.seg_cnt, g.nseg, w.n,
+                                                                 w.slots);
         CHECK_LAUNCH();
-        k_merge_tile_sums<<<uint32_t(ntiles), kScanThreads, 0, s>>>(slots, n, sums, ntiles);
-        CHECK_LAUNCH();
-        k_merge_tile_scan<<<1, kScanThreads, 0, s>>>(sums, ntiles, totals);
-        CHECK_LAUNCH();
-        HIP_TRY(hipMemcpyAsync(tot, totals, sizeof tot, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
     }
-    *n_out = tot[0];
-    *key_bytes_out = tot[1];
-    *value_bytes_out = tot[2];
-    if (tot[0] + 1 > offsets_cap)
-        return fail(PBF_ERR_INVALID, "the run holds " + std::to_string(tot[0]) + " records: each offsets array needs " +
-                                         std::to_string(tot[0] + 1) + " entries, offsets_cap is " +
-                                         std::to_string(offsets_cap));
-    if (tot[1] > keys_cap || (tot[1] && !keys_out))
-        return fail(PBF_ERR_INVALID, "the keys need " + std::to_string(tot[1]) + " bytes, keys_out holds " +
-                                         std::to_string(keys_out ? keys_cap : 0));
-    if (tot[2] > values_cap || (tot[2] && !values_out))
-        return fail(PBF_ERR_INVALID, "the values need " + std::to_string(tot[2]) + " bytes, values_out holds " +
-                                         std::to_string(values_out ? values_cap : 0));
-    uint8_t *dk = keys_out, *dv = values_out;
-    uint64_t *dko = key_offsets_out, *dvo = value_offsets_out, *dro = range_offsets_out;
+    uint64_t* dro = range_offsets_out;
     if (!on_device) {
-        HIP_TRY(c.mkeys.ensure(tot[1] + 16));
-        HIP_TRY(c.mvals.ensure(tot[2] + 16));
-        HIP_TRY(c.mko.ensure((tot[0] + 1) * 8));
-        HIP_TRY(c.mvo.ensure((tot[0] + 1) * 8));
         HIP_TRY(c.sro.ensure((nranges + 1) * 8));
-        dk = static_cast<uint8_t*>(c.mkeys.p);
-        dv = static_cast<uint8_t*>(c.mvals.p);
-        dko = static_cast<uint64_t*>(c.mko.p);
-        dvo = static_cast<uint64_t*>(c.mvo.p);
         dro = static_cast<uint64_t*>(c.sro.p);
     }
-    if (n) {
-        k_merge_offsets<<<uint32_t(ntiles), kScanThreads, 0, s>>>(slots, n, sums, ntiles, pos, dko, dvo);
-        CHECK_LAUNCH();
-        k_merge_copy<<<grid_for(n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(g.set, slots, n, pos, totals, dko, dvo, dk,
-                                                                              dv);
-        CHECK_LAUNCH();
-        k_scan_range_offsets<<<grid_for(nranges + 1, 256, 1u << 20), 256, 0, s>>>(g.seg_base, ntables, nranges, slots, n,
-                                                                                  pos, sums, totals, dro);
-        CHECK_LAUNCH();
-    } else {  // an empty run: both offsets arrays are {0}, every range is empty
-        HIP_TRY(hipMemsetAsync(dko, 0, 8, s));
-        HIP_TRY(hipMemsetAsync(dvo, 0, 8, s));
-        HIP_TRY(hipMemsetAsync(dro, 0, (nranges + 1) * 8, s));
-    }
-    if (on_device) {
-        if (!c.merge_done) HIP_TRY(hipEventCreateWithFlags(&c.merge_done, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c.merge_done, s));
-        return locks.used_on(s);
-    }
-    HIP_TRY(hipMemcpyAsync(key_offsets_out, dko, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(value_offsets_out, dvo, (tot[0] + 1) * 8, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(range_offsets_out, dro, (nranges + 1) * 8, hipMemcpyDeviceToHost, s));
-    if (tot[1]) HIP_TRY(hipMemcpyAsync(keys_out, dk, tot[1], hipMemcpyDeviceToHost, s));
-    if (tot[2]) HIP_TRY(hipMemcpyAsync(values_out, dv, tot[2], hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return PBF_OK;
+    // the ranges' offsets into the run, behind its copy kernel; an empty run's ranges are all empty
+    return run_emit(c, locks, g.set, w, o, [&] {
+        if (w.n) {
+            k_scan_range_offsets<<<grid_for(nranges + 1, 256, 1u << 20), 256, 0, s>>>(g.seg_base, ntables, nranges, w.slots,
+                                                                                      w.n, w.pos, w.sums, w.totals, dro);
+            CHECK_LAUNCH();
+        } else {
+            HIP_TRY(hipMemsetAsync(dro, 0, (nranges + 1) * 8, s));
+        }
+        if (!on_device) HIP_TRY(hipMemcpyAsync(range_offsets_out, dro, (nranges + 1) * 8, hipMemcpyDeviceToHost, s));
+        return int(PBF_OK);
+    });
 }
 
 }  // extern "C"

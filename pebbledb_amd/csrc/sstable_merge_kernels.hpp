@@ -12,6 +12,8 @@
 //     probe, and whether that key equals it: sst_find's two binary searches (blocks by
 //     last_prefix, records by the u16 array), plus rec_base[nblocks+1], the prefix sum of the
 //     validated index's block counts.
+//   * merge_record_at — record i of a table: its block by a binary search over rec_base, its slot
+//     through the block's u16 array.  The scan's kernels walk to their records with it too.
 //   * k_merge_rank — one lane per input record (t, i): rank = i + sum over u<t of (lb_u + eq_u)
 //     + sum over u>t of lb_u is the record's place among ALL input records ordered by (key,
 //     table), a permutation of [0, N); keep = no table u<t holds the key.  Concatenate mode runs
@@ -100,6 +102,30 @@ __device__ __forceinline__ uint32_t sst_lower_bound(const SstView& t, const uint
     return gld(rec_base + lo) + a;
 }
 
+// Record i of table t (its block through rec_base, its slot through the u16 array): the record's
+// offset in the data section, *kl / *vl = its header.  The one record walk: k_merge_rank,
+// k_scan_rank and k_scan_sizes (sstable_scan_kernels.hpp) all find their record here.
+__device__ __forceinline__ uint32_t merge_record_at(const MergeSet& set, uint32_t t, uint32_t i, uint32_t* kl,
+                                                    uint32_t* vl) {
+    const uint32_t* rb = set.rec_base[t];
+    uint32_t lo = 0, hi = set.nblocks[t];  // rec_base[lo] <= i < rec_base[hi]
+    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (gld(rb + mid) <= i)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const SstBlock blk = ld_block(set.index[t] + lo);
+    const uint32_t slot = min(i - gld(rb + lo), blk.count - 1);  // (inside the block whatever rec_base holds)
+    const uint8_t* data = set.data[t];
+    const uint32_t rec_off = blk.first_off + ld_u16(data + blk.u16_off + 2 * slot);
+    const uint8_t* r = data + rec_off;
+    *kl = uint32_t(ld_i32(r));
+    *vl = uint32_t(ld_i32(r + 4 + *kl));
+    return rec_off;
+}
+
 // dedup = 1: MergingIterator; 0: ConcatenatingIterator.  n = the tables' records together.
 __global__ void __launch_bounds__(256) k_merge_rank(MergeSet set, uint64_t n, int dedup, MergeSlot* __restrict__ slots) {
     const uint64_t stride = uint64_t(gridDim.x) * blockDim.x;
@@ -108,24 +134,9 @@ __global__ void __launch_bounds__(256) k_merge_rank(MergeSet set, uint64_t n, in
         uint32_t t = 0;
         for (uint32_t u = 1; u < set.nt; ++u) t += set.in_base[u] <= g;
         const uint32_t i = uint32_t(g - set.in_base[t]);
-        // its block: the last b with rec_base[b] <= i
-        const uint32_t* rb = set.rec_base[t];
-        uint32_t lo = 0, hi = set.nblocks[t];  // rec_base[lo] <= i < rec_base[hi]
-        for (int it = 0; it < 32 && hi - lo > 1; ++it) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if (gld(rb + mid) <= i)
-                lo = mid;
-            else
-                hi = mid;
-        }
-        const SstBlock blk = ld_block(set.index[t] + lo);
-        const uint32_t slot = min(i - gld(rb + lo), blk.count - 1);  // (inside the block whatever rec_base holds)
-        const uint8_t* data = set.data[t];
-        const uint32_t rec_off = blk.first_off + ld_u16(data + blk.u16_off + 2 * slot);
-        const uint8_t* r = data + rec_off;
-        const uint32_t kl = uint32_t(ld_i32(r));
-        const uint8_t* key = r + 4;
-        const uint32_t vl = uint32_t(ld_i32(key + kl));
+        uint32_t kl, vl;
+        const uint32_t rec_off = merge_record_at(set, t, i, &kl, &vl);
+        const uint8_t* key = set.data[t] + rec_off + 4;
         uint64_t rank = g;
         uint32_t keep = kMergeKeep;
         if (dedup) {

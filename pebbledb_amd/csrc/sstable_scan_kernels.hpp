@@ -17,7 +17,8 @@
 //   * k_scan_sizes — the key and value bytes of the N selected records (before de-duplication).
 //   * k_scan_rank — one lane per selected record g: its segment is the last s with
 //     seg_base[s] <= g (empty segments share a base: the last one is the one that holds g),
-//     j = g - seg_base[s], table-wide index i = seg_lo[s] + j;
+//     j = g - seg_base[s], table-wide index i = seg_lo[s] + j (the record itself through
+//     sstable_merge_kernels.hpp's merge_record_at, as in k_merge_rank and k_scan_sizes);
 //         rank = seg_base[q*T] + j + sum over u<t of (lb_u + eq_u - lo_u) + sum over u>t of (lb_u - lo_u)
 //         keep = no table u<t holds the key
 //     where (lb_u, eq_u) = sst_lower_bound(table u, key) and lo_u = seg_lo[q*T + u].  The key lies
@@ -98,29 +99,6 @@ __device__ __forceinline__ uint64_t scan_segment_of(const uint64_t* __restrict__
     return lo;
 }
 
-// Record i of table t (k_merge_rank's walk: its block through rec_base, its slot through the u16
-// array): the record's offset in the data section, *kl / *vl = its header.
-__device__ __forceinline__ uint32_t scan_record_at(const MergeSet& set, uint32_t t, uint32_t i, uint32_t* kl,
-                                                   uint32_t* vl) {
-    const uint32_t* rb = set.rec_base[t];
-    uint32_t lo = 0, hi = set.nblocks[t];  // rec_base[lo] <= i < rec_base[hi]
-    for (int it = 0; it < 32 && hi - lo > 1; ++it) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (gld(rb + mid) <= i)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const SstBlock blk = ld_block(set.index[t] + lo);
-    const uint32_t slot = min(i - gld(rb + lo), blk.count - 1);  // (inside the block whatever rec_base holds)
-    const uint8_t* data = set.data[t];
-    const uint32_t rec_off = blk.first_off + ld_u16(data + blk.u16_off + 2 * slot);
-    const uint8_t* r = data + rec_off;
-    *kl = uint32_t(ld_i32(r));
-    *vl = uint32_t(ld_i32(r + 4 + *kl));
-    return rec_off;
-}
-
 // totals[0] += the key bytes, totals[1] += the value bytes of the n selected records (totals
 // zeroed before the launch).
 __global__ void __launch_bounds__(kScanThreads) k_scan_sizes(MergeSet set, const uint64_t* __restrict__ seg_base,
@@ -134,7 +112,7 @@ __global__ void __launch_bounds__(kScanThreads) k_scan_sizes(MergeSet set, const
         const uint32_t t = uint32_t(s % set.nt);
         const uint32_t i = gld(seg_lo + s) + uint32_t(g - gld(seg_base + s));
         uint32_t kl, vl;
-        scan_record_at(set, t, i, &kl, &vl);
+        merge_record_at(set, t, i, &kl, &vl);
         kb += kl;
         vb += vl;
     }
@@ -159,7 +137,7 @@ __global__ void __launch_bounds__(256) k_scan_rank(MergeSet set, const uint64_t*
         const uint64_t s0 = s - t;  // q * T
         const uint32_t j = uint32_t(g - gld(seg_base + s));
         uint32_t kl, vl;
-        const uint32_t rec_off = scan_record_at(set, t, gld(seg_lo + s) + j, &kl, &vl);
+        const uint32_t rec_off = merge_record_at(set, t, gld(seg_lo + s) + j, &kl, &vl);
         const uint8_t* key = set.data[t] + rec_off + 4;
         const uint64_t kpre = key_prefix(key, kl);
         const uint64_t first = gld(seg_base + s0), end = gld(seg_base + s0 + set.nt);  // the range's span

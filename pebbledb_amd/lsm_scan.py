@@ -38,21 +38,12 @@ from typing import Sequence
 import numpy as np
 
 from . import _native
-from .compaction import MAX_TABLES
-from .keys import PackedKeys, PackedRecords
+from .compaction import _RunOut, _table_list
+from .keys import PackedRecords
 from .sstable_read import _handles
 
 _vp = ctypes.c_void_p
 MAX_SEGMENTS = 1 << 22  # PBF_SCAN_MAX_SEGMENTS: ranges x tables of one call
-
-
-def _tables(tables) -> list:
-    tables = list(tables)
-    if not tables:
-        raise ValueError("no tables to scan")
-    if len(tables) > MAX_TABLES:
-        raise ValueError(f"a scan takes at most {MAX_TABLES} tables, got {len(tables)}")
-    return tables
 
 
 class _Bounds:
@@ -107,24 +98,15 @@ def scan_ranges(tables: Sequence, ranges) -> tuple[PackedRecords, np.ndarray]:
     range what ``scan_tables(tables, lower, upper)`` gives.  Ranges may overlap, repeat and come
     in any order; a record in two ranges appears in both.  At most 64 tables, all open, distinct
     and on one device, and at most 2**22 ranges x tables (ValueError otherwise)."""
-    tables = _tables(tables)
+    tables = _table_list(tables, "scan")
     b = _Bounds(ranges)
     hs = _handles(tables)
     n, kbytes, vbytes, _, _ = _size(hs, len(tables), b, False)
-    keys = np.empty(kbytes, dtype=np.uint8)
-    values = np.empty(vbytes, dtype=np.uint8)
-    ko = np.empty(n + 1, dtype=np.uint64)
-    vo = np.empty(n + 1, dtype=np.uint64)
+    out = _RunOut(n, kbytes, vbytes)
     ro = np.zeros(b.n + 1, dtype=np.uint64)
-    n_out, kb, vb = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    rc = _native.lib().pbf_sst_scan(hs, len(tables), *b.args(), _vp(keys.ctypes.data) if kbytes else None, kbytes,
-                                    _vp(ko.ctypes.data), _vp(values.ctypes.data) if vbytes else None, vbytes,
-                                    _vp(vo.ctypes.data), n + 1, ctypes.byref(n_out), ctypes.byref(kb), ctypes.byref(vb),
-                                    _vp(ro.ctypes.data), 0, None)
+    rc = _native.lib().pbf_sst_scan(hs, len(tables), *b.args(), *out.args(), _vp(ro.ctypes.data), 0, None)
     _native.check(rc, "pbf_sst_scan")
-    m = n_out.value
-    pk = PackedKeys(keys[:kb.value], m, offsets=ko[:m + 1])
-    return PackedRecords(pk, values[:vb.value], vo[:m + 1]), ro
+    return out.records(), ro
 
 
 def scan_tables(tables: Sequence, lower: str, upper: str) -> PackedRecords:
@@ -136,7 +118,7 @@ def scan_tables(tables: Sequence, lower: str, upper: str) -> PackedRecords:
 def count_ranges(tables: Sequence, ranges) -> np.ndarray:
     """int64[Q, T]: the records of table t in range q (before any de-duplication across tables).
     One ``pbf_sst_scan_size`` call: two searches per entry, no record is copied."""
-    tables = _tables(tables)
+    tables = _table_list(tables, "scan")
     b = _Bounds(ranges)
     _, _, _, lo, hi = _size(_handles(tables), len(tables), b, True)
     return hi.astype(np.int64) - lo.astype(np.int64)

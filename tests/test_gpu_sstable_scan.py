@@ -500,6 +500,60 @@ def test_device_pointer_form_equals_host_form(opened):
             assert np.array_equal(host[x][:m], dev[x][:m]), x
 
 
+@pytest.mark.timeout(150)
+def test_device_form_calls_back_to_back_on_two_streams(opened):
+    """A merge on one stream, a scan on a second and a merge on the first again, all in the device
+    form with no synchronise between them: the three share the context's working memory, so each
+    has to wait for the one before it.  One synchronise at the end; every output equals the host
+    form's, and the guard words past every capacity are intact."""
+    tables, rows = three_tables(opened)
+    hs = (vp * len(tables))(*[t._h.value for t in tables])
+    merged = merge_tables(tables)  # the host form
+    host = scan_call(tables, COPY_RANGES)
+    assert host["rc"] == 0 and records_of(merged) == [(x, v) for x, v, _ in MM.merge(rows)]
+    b = _Bounds(COPY_RANGES)
+    pad, pattern = 64, host["pattern"]
+
+    def device_bufs(n, kb, vb):
+        byte = {x: torch.full((s + pad,), GUARD, dtype=torch.uint8, device="cuda")
+                for x, s in (("keys", kb), ("values", vb))}
+        offs = {x: torch.from_numpy(np.full(s + pad, pattern).view(np.int64)).cuda()
+                for x, s in (("ko", n + 1), ("vo", n + 1), ("ro", b.n + 1))}
+        return dict(n=n, kb=kb, vb=vb, tot=[ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()], **byte, **offs)
+
+    def out_args(d):
+        return (vp(d["keys"].data_ptr()), d["kb"], vp(d["ko"].data_ptr()), vp(d["values"].data_ptr()), d["vb"],
+                vp(d["vo"].data_ptr()), d["n"] + 1, *[ctypes.byref(x) for x in d["tot"]])
+
+    first, second = (device_bufs(merged.n, len(merged.keys.data), len(merged.values)) for _ in range(2))
+    scanned = device_bufs(host["n"], host["kb"], host["vb"])
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    torch.cuda.synchronize()  # the guard patterns are in place
+    L = _native.lib()
+    rcs = [L.pbf_sst_merge(hs, len(tables), 0, *out_args(first), 1, vp(sa.cuda_stream)),
+           L.pbf_sst_scan(hs, len(tables), *b.args(), *out_args(scanned), vp(scanned["ro"].data_ptr()), 1,
+                          vp(sb.cuda_stream)),
+           L.pbf_sst_merge(hs, len(tables), 0, *out_args(second), 1, vp(sa.cuda_stream))]
+    torch.cuda.synchronize()
+    assert rcs == [0, 0, 0], L.pbf_last_error()
+
+    def check(d, want):
+        """want = the host form's (keys, key offsets, values, value offsets[, range offsets])."""
+        assert [x.value for x in d["tot"]] == [d["n"], d["kb"], d["vb"]]
+        for x, w in zip(("keys", "ko", "values", "vo", "ro"), want):
+            got = d[x].cpu().numpy()
+            got, guard = (got, GUARD) if got.dtype == np.uint8 else (got.view(np.uint64), pattern)
+            assert np.array_equal(got[:len(w)], w), x
+            assert (got[len(w):] == guard).all(), x
+
+    m = merged.n
+    for d in (first, second):
+        check(d, (merged.keys.data, merged.keys.offsets[:m + 1], np.asarray(merged.values), merged.value_offsets[:m + 1]))
+    n = host["n"]
+    check(scanned, (host["keys"][:host["kb"]], host["ko"][:n + 1], host["values"][:host["vb"]], host["vo"][:n + 1],
+                    host["ro"][:b.n + 1]))
+
+
 @pytest.mark.parametrize("device", [False, True], ids=["host", "device"])
 def test_capacity_one_too_small_is_refused(opened, device):
     """The keys' and the values' capacity one byte short, and offsets_cap (the one capacity of
