@@ -458,6 +458,34 @@ int pbf_sst_scan(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* 
                  uint64_t* key_bytes_out, uint64_t* value_bytes_out, uint64_t* range_offsets_out, int on_device,
                  void* stream);
 
+/* ---- Memtable flush: MemTableIterator's run (src/iterators.py:24-55) of a put log: every distinct
+ * key in ascending unsigned bytewise order, each with the value of its LAST put (the memtable's
+ * tree replaces the data of a key it holds, src/red_black_tree.py:118-120; an empty value is a
+ * value like any other).  The log is the n puts in put order, packed as pbf_build_sstable reads
+ * records: put i = keys[key_offsets[i], key_offsets[i+1]), values[value_offsets[i],
+ * value_offsets[i+1]).  Inputs and outputs are host memory; synchronous.
+ * The output layout, the totals and the capacity rules are pbf_sst_merge's: both offsets arrays
+ * receive *n_out + 1 entries; the totals are set whenever the run was counted, also when it does
+ * not fit, and then nothing is written and the message states the size needed.
+ * put_index_out (NULL, or offsets_cap entries): put_index_out[j] = the log index of the put that
+ * record j came from.  n == 0: PBF_OK, an empty run (both offsets arrays = {0}).
+ * PBF_ERR_INVALID, checked on the host before any launch: offsets that do not start at 0 or that
+ * descend; n >= 2^32 - 1; a key or value of 2^31 bytes or more; a null pointer. */
+int pbf_log_sort(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
+                 const uint64_t* value_offsets, uint64_t n,
+                 uint8_t* keys_out, uint64_t keys_cap, uint64_t* key_offsets_out,
+                 uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
+                 uint64_t offsets_cap, uint32_t* put_index_out /* NULL, or offsets_cap entries */,
+                 uint64_t* n_out, uint64_t* key_bytes_out, uint64_t* value_bytes_out);
+
+/* Device time of the last successful pbf_log_sort on `device`, by stage (HIP events on the call's
+ * stream; tools/bench_flush.py): upload of the log, k_mt_entries, k_mt_tile_sort, the merge
+ * passes together, k_mt_mark, the scans and offsets (with the read-back of the totals between
+ * them), k_mt_copy, download of the run.  ms_out receives PBF_LOG_SORT_STAGES entries;
+ * *merge_passes_out (or NULL) the k_mt_merge_rank launches. */
+#define PBF_LOG_SORT_STAGES 8
+int pbf_log_sort_stage_ms(int device, float* ms_out, uint32_t* merge_passes_out);
+
 /* Synthetic keys straight into device memory (bench / tests; definitions in
  * pebbledb_amd/keys.py): 16 hex chars of splitmix64(seed + start + i), and the variable-length
  * 8..64-byte family (offsets must already hold the n+1 offsets, relative to offsets[0]).

@@ -7,8 +7,9 @@ from .bloom_filter import BloomFilter, may_contain_multi, may_contain_set, probe
 from .compaction import compact_l0, compact_level, concat_tables, merge_tables
 from .keys import PackedKeys
 from .lsm_scan import count_ranges, scan_ranges, scan_tables
+from .memtable import flush_log, flush_wal, sort_log
 from .sstable_read import DeviceSSTable
 
 __all__ = ["BloomFilter", "DeviceSSTable", "PackedKeys", "compact_l0", "compact_level", "concat_tables",
-           "count_ranges", "may_contain_multi", "may_contain_set", "merge_tables", "probe_multi_device",
-           "scan_ranges", "scan_tables", "set_default_device"]
+           "count_ranges", "flush_log", "flush_wal", "may_contain_multi", "may_contain_set", "merge_tables",
+           "probe_multi_device", "scan_ranges", "scan_tables", "set_default_device", "sort_log"]

@@ -94,6 +94,9 @@ SIGNATURES = {
                                  ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "pbf_sst_scan": (_int, [_vp, _u32, _u8p, _vp, _u8p, _vp, _u8p, _u64, _u8p, _u64, _vp, _u8p, _u64, _vp, _u64,
                             ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _int, _vp]),
+    "pbf_log_sort": (_int, [_int, _u8p, _vp, _u8p, _vp, _u64, _u8p, _u64, _vp, _u8p, _u64, _vp, _u64, _vp,
+                            ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "pbf_log_sort_stage_ms": (_int, [_int, _vp, ctypes.POINTER(_u32)]),
     "pbf_gen_splitmix_hex": (_int, [_int, _vp, _u8p, _u64, _u64, _u64]),
     "pbf_gen_varlen": (_int, [_int, _vp, _u8p, _vp, _u64, _u64, _u64]),
     "pbf_last_error": (ctypes.c_char_p, []),

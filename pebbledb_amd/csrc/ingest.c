@@ -530,6 +530,92 @@ fail:
     return NULL;
 }
 
+/* pack_wal(bytes-like) — a write-ahead log as WriteAheadLog.read_records reads it (wal.py:29-31,
+ * Record.list_from_bytes record.py:93-100): Record.to_bytes() of every put back to back, in put
+ * order.  Every record is split by pack_encoded's rules (negative sizes, UTF-8 validity, the
+ * ascii flag); duplicate keys are kept, in log order.  A stream that ends inside a record is
+ * refused with a ValueError that states the byte offset of the torn record (the reference's
+ * slicing would hand on a clipped key or value). */
+static PyObject* py_pack_wal(PyObject* self, PyObject* args) {
+    Py_buffer view;
+    if (!PyArg_ParseTuple(args, "y*", &view)) return NULL;
+    const unsigned char* d = (const unsigned char*)view.buf;
+    const size_t L = (size_t)view.len;
+    Buf kb = {0}, ko = {0}, vb = {0}, vo = {0};
+    uint64_t n = 0, min_len = UINT64_MAX, max_len = 0;
+    int ascii = 1;
+    size_t at = 0;
+    const char* part = "header";
+    if (buf_u64(&ko, 0) || buf_u64(&vo, 0)) goto fail;
+    while (at < L) {
+        int32_t ks, vs;
+        part = "header";
+        if (L - at < 4) goto torn;
+        memcpy(&ks, d + at, 4);
+        if (ks < 0) goto neg;
+        part = "key";
+        if (L - at - 4 < (size_t)ks) goto torn;
+        const unsigned char* key = d + at + 4;
+        const size_t kl = (size_t)ks;
+        int all_ascii = 1;
+        for (size_t c = 0; c < kl; ++c)
+            if (key[c] & 0x80) {
+                all_ascii = 0;
+                break;
+            }
+        if (!all_ascii) {  // the reference decodes: invalid UTF-8 raises there too
+            ascii = 0;
+            PyObject* u = PyUnicode_DecodeUTF8((const char*)key, (Py_ssize_t)kl, NULL);
+            if (!u) goto fail;
+            Py_DECREF(u);
+        }
+        const size_t v0 = at + 4 + kl + 4;
+        part = "value size";
+        if (L - at - 4 - kl < 4) goto torn;
+        memcpy(&vs, d + v0 - 4, 4);
+        if (vs < 0) goto neg;
+        part = "value";
+        if (L - v0 < (size_t)vs) goto torn;
+        if (buf_put(&kb, key, kl) || buf_u64(&ko, kb.n) || buf_put(&vb, d + v0, (size_t)vs) || buf_u64(&vo, vb.n))
+            goto fail;
+        if ((uint64_t)kl < min_len) min_len = (uint64_t)kl;
+        if ((uint64_t)kl > max_len) max_len = (uint64_t)kl;
+        at = v0 + (size_t)vs;
+        ++n;
+    }
+    PyBuffer_Release(&view);
+    if (n == 0) min_len = 0;
+    {
+        PyObject* a = buf_release(&kb);
+        PyObject* b = buf_release(&ko);
+        PyObject* c = buf_release(&vb);
+        PyObject* e = buf_release(&vo);
+        if (!a || !b || !c || !e) {
+            Py_XDECREF(a);
+            Py_XDECREF(b);
+            Py_XDECREF(c);
+            Py_XDECREF(e);
+            return NULL;
+        }
+        return Py_BuildValue("(NNNNKiKK)", a, b, c, e, (unsigned long long)n, ascii, (unsigned long long)min_len,
+                             (unsigned long long)max_len);
+    }
+torn:
+    PyErr_Format(PyExc_ValueError, "pack_wal: the record at byte offset %zu (record %llu) is torn: the stream of %zu "
+                 "bytes ends inside its %s", at, (unsigned long long)n, L, part);
+    goto fail;
+neg:
+    PyErr_Format(PyExc_ValueError, "pack_wal: negative key or value size in the record at byte offset %zu (record %llu)",
+                 at, (unsigned long long)n);
+fail:
+    PyBuffer_Release(&view);
+    buf_free(&kb);
+    buf_free(&ko);
+    buf_free(&vb);
+    buf_free(&vo);
+    return NULL;
+}
+
 static PyObject* py_pack_keys(PyObject* self, PyObject* args) {
     PyObject* iterable;
     if (!PyArg_ParseTuple(args, "O", &iterable)) return NULL;
@@ -550,6 +636,8 @@ static PyMethodDef methods[] = {
      "max_len)"},
     {"pack_encoded", py_pack_encoded, METH_VARARGS,
      "pack_encoded(iterable of Record.to_bytes() bytes) -> as pack_records (split as Record._from_bytes)"},
+    {"pack_wal", py_pack_wal, METH_VARARGS,
+     "pack_wal(bytes-like WAL stream) -> as pack_records, records in log order (a torn stream raises ValueError)"},
     {NULL, NULL, 0, NULL},
 };
 

@@ -37,6 +37,7 @@
 #include "sstable_read_kernels.hpp"
 #include "sstable_merge_kernels.hpp"
 #include "sstable_scan_kernels.hpp"
+#include "memtable_kernels.hpp"
 
 using namespace pbf;
 
@@ -3600,6 +3601,13 @@ struct SstCtx {
     hipEvent_t merge_done = nullptr;
     // pbf_sst_scan's bounds, segment arrays and (host form) range offsets: under merge_done too
     DevBuf sbnd, sseg, sro;
+    // pbf_log_sort's copy of the put log, its two entry buffers and the put indices of its run
+    // (under merge_done too); log_ev = the stage marks of the last call, log_ms their gaps
+    DevBuf lkeys, lko, lvals, lvo, lent[2], lput;
+    hipEvent_t log_ev[PBF_LOG_SORT_STAGES + 1] = {};
+    float log_ms[PBF_LOG_SORT_STAGES] = {};
+    uint32_t log_passes = 0;
+    bool log_timed = false;
 };
 
 SstCtx& sst_ctx(int device) {
@@ -4045,6 +4053,16 @@ struct RunWork {
     uint64_t *pos = nullptr, *sums = nullptr, *totals = nullptr;
 };
 
+// k_merge_copy over the tables of `set`, as run_emit launches it for a merge or a scan.
+auto merge_copy_launch(const MergeSet& set, const RunWork& w, hipStream_t s) {
+    return [&set, &w, s](uint64_t* dko, uint64_t* dvo, uint8_t* dk, uint8_t* dv) {
+        k_merge_copy<<<grid_for(w.n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(set, w.slots, w.n, w.pos, w.totals, dko,
+                                                                                 dvo, dk, dv);
+        CHECK_LAUNCH();
+        return int(PBF_OK);
+    };
+}
+
 // Sizes the working memory for n input records and zeroes the slots on o.s; the caller's rank
 // kernel fills them next.  n == 0 needs none.  The caller holds c.mu and has waited for
 // merge_done, as for everything below.
@@ -4066,12 +4084,14 @@ int run_prepare(SstCtx& c, const RunOut& o, uint64_t n, RunWork& w) {
 }
 
 // From the ranked slots to the end of the call: the totals (one sync; reported before any
-// refusal, for the retry), the capacities, the offsets and the bytes of the run.  `extra()`
+// refusal, for the retry), the capacities, the offsets and the bytes of the run.
+// `copy(key_offsets, value_offsets, keys, values)` launches the door's copy kernel (k_merge_copy
+// over a MergeSet, k_mt_copy over a put log) into the device form of the outputs; `extra()`
 // queues what else the door wants on o.s once the run is queued, while the working memory is
 // still its own.  Then the device form records merge_done and the tables' use; the host form
 // copies the run back and waits.  An empty run (n == 0) is the two offsets arrays {0}.
-template <class Extra>
-int run_emit(SstCtx& c, SstLocks& locks, const MergeSet& set, const RunWork& w, const RunOut& o, Extra extra) {
+template <class Copy, class Extra>
+int run_emit(SstCtx& c, SstLocks& locks, const RunWork& w, const RunOut& o, Copy copy, Extra extra) {
     hipStream_t s = o.s;
     uint64_t tot[kMergeTotals] = {0, 0, 0};
     if (w.n) {
@@ -4110,9 +4130,8 @@ int run_emit(SstCtx& c, SstLocks& locks, const MergeSet& set, const RunWork& w, 
     if (w.n) {
         k_merge_offsets<<<uint32_t(w.ntiles), kScanThreads, 0, s>>>(w.slots, w.n, w.sums, w.ntiles, w.pos, dko, dvo);
         CHECK_LAUNCH();
-        k_merge_copy<<<grid_for(w.n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(set, w.slots, w.n, w.pos, w.totals, dko,
-                                                                                 dvo, dk, dv);
-        CHECK_LAUNCH();
+        int rc = copy(dko, dvo, dk, dv);
+        if (rc) return rc;
     } else {
         HIP_TRY(hipMemsetAsync(dko, 0, 8, s));
         HIP_TRY(hipMemsetAsync(dvo, 0, 8, s));
@@ -4164,7 +4183,7 @@ int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint
     if ((rc = run_prepare(c, o, n, w))) return rc;
     k_merge_rank<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(set, n, mode == PBF_MERGE_DEDUP, w.slots);
     CHECK_LAUNCH();
-    return run_emit(c, locks, set, w, o, [] { return int(PBF_OK); });
+    return run_emit(c, locks, w, o, merge_copy_launch(set, w, s), [] { return int(PBF_OK); });
 }
 
 }  // extern "C"
@@ -4345,7 +4364,7 @@ int pbf_sst_scan(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* 
         dro = static_cast<uint64_t*>(c.sro.p);
     }
     // the ranges' offsets into the run, behind its copy kernel; an empty run's ranges are all empty
-    return run_emit(c, locks, g.set, w, o, [&] {
+    return run_emit(c, locks, w, o, merge_copy_launch(g.set, w, s), [&] {
         if (w.n) {
             k_scan_range_offsets<<<grid_for(nranges + 1, 256, 1u << 20), 256, 0, s>>>(g.seg_base, ntables, nranges, w.slots,
                                                                                       w.n, w.pos, w.sums, w.totals, dro);
@@ -4356,6 +4375,141 @@ int pbf_sst_scan(pbf_sstable_t* const* tables, uint32_t ntables, const uint8_t* 
         if (!on_device) HIP_TRY(hipMemcpyAsync(range_offsets_out, dro, (nranges + 1) * 8, hipMemcpyDeviceToHost, s));
         return int(PBF_OK);
     });
+}
+
+}  // extern "C"
+
+// ====================================================================== memtable flush
+// MemTableIterator's run of a put log (csrc/memtable_kernels.hpp): sort by (key, put index), keep
+// the last put of every key, then the merge's scans and one packed copy.
+namespace {
+
+// The offsets of a packed log: from 0, ascending, every item shorter than 2^31 bytes.
+int check_log_offsets(const uint64_t* o, uint64_t n, const char* what) {
+    if (o[0] != 0) return fail(PBF_ERR_INVALID, std::string(what) + " offsets must start at 0");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (o[i + 1] < o[i])
+            return fail(PBF_ERR_INVALID, std::string(what) + " offsets must ascend (entry " + std::to_string(i + 1) + ")");
+        if (o[i + 1] - o[i] > 0x7FFFFFFFull)
+            return fail(PBF_ERR_INVALID, std::string("put ") + std::to_string(i) + ": a " + what + " of 2^31 bytes or more");
+    }
+    return PBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbf_log_sort(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
+                 const uint64_t* value_offsets, uint64_t n, uint8_t* keys_out, uint64_t keys_cap,
+                 uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
+                 uint64_t offsets_cap, uint32_t* put_index_out, uint64_t* n_out, uint64_t* key_bytes_out,
+                 uint64_t* value_bytes_out) {
+    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out)
+        return fail(PBF_ERR_INVALID, "null pointer");
+    if (n >= 0xFFFFFFFFull) return fail(PBF_ERR_INVALID, "a put log holds fewer than 2^32 - 1 puts, got " + std::to_string(n));
+    int rc;
+    if (n) {
+        if (!key_offsets || !value_offsets) return fail(PBF_ERR_INVALID, "null pointer");
+        if ((rc = check_log_offsets(key_offsets, n, "key"))) return rc;
+        if ((rc = check_log_offsets(value_offsets, n, "value"))) return rc;
+        if ((key_offsets[n] && !keys) || (value_offsets[n] && !values)) return fail(PBF_ERR_INVALID, "null pointer");
+    }
+    const uint64_t kbytes = n ? key_offsets[n] : 0, vbytes = n ? value_offsets[n] : 0;
+    HIP_TRY(hipSetDevice(device));
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    if ((rc = sst_ctx_stream(c, device))) return rc;
+    if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
+    hipStream_t s = c.stream;
+    for (hipEvent_t& e : c.log_ev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    c.log_timed = false;
+    c.log_passes = 0;
+    int stage = 0;
+    auto mark = [&]() -> int {
+        HIP_TRY(hipEventRecord(c.log_ev[stage++], s));
+        return PBF_OK;
+    };
+    const RunOut o{keys_out, keys_cap, key_offsets_out, values_out, values_cap, value_offsets_out, offsets_cap,
+                   n_out, key_bytes_out, value_bytes_out, 0, s};
+    RunWork w;
+    if ((rc = run_prepare(c, o, n, w))) return rc;
+    MtLog log{};
+    MtEntry* sorted = nullptr;
+    if ((rc = mark())) return rc;  // 0: upload
+    if (n) {
+        HIP_TRY(c.lkeys.ensure(kbytes + 16));
+        HIP_TRY(c.lvals.ensure(vbytes + 16));
+        HIP_TRY(c.lko.ensure((n + 1) * 8));
+        HIP_TRY(c.lvo.ensure((n + 1) * 8));
+        HIP_TRY(c.lent[0].ensure(n * sizeof(MtEntry)));
+        HIP_TRY(c.lent[1].ensure(n * sizeof(MtEntry)));
+        if (put_index_out) HIP_TRY(c.lput.ensure(n * 4));
+        if (kbytes) HIP_TRY(hipMemcpyAsync(c.lkeys.p, keys, kbytes, hipMemcpyHostToDevice, s));
+        if (vbytes) HIP_TRY(hipMemcpyAsync(c.lvals.p, values, vbytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c.lko.p, key_offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(c.lvo.p, value_offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+        log = MtLog{static_cast<const uint8_t*>(c.lkeys.p), static_cast<const uint64_t*>(c.lko.p),
+                    static_cast<const uint8_t*>(c.lvals.p), static_cast<const uint64_t*>(c.lvo.p), n};
+        MtEntry* ent[2] = {static_cast<MtEntry*>(c.lent[0].p), static_cast<MtEntry*>(c.lent[1].p)};
+        if ((rc = mark())) return rc;  // 1: entries
+        k_mt_entries<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(log, ent[0]);
+        CHECK_LAUNCH();
+        if ((rc = mark())) return rc;  // 2: tile sort
+        k_mt_tile_sort<<<uint32_t(w.ntiles), kMtSortThreads, 0, s>>>(log, ent[0]);
+        CHECK_LAUNCH();
+        if ((rc = mark())) return rc;  // 3: merge passes
+        int cur = 0;
+        for (uint64_t run = kMtTile; run < n; run *= kMtFanIn) {
+            k_mt_merge_rank<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(log, ent[cur], ent[cur ^ 1], run);
+            CHECK_LAUNCH();
+            cur ^= 1;
+            ++c.log_passes;
+        }
+        sorted = ent[cur];
+        if ((rc = mark())) return rc;  // 4: mark
+        k_mt_mark<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(log, sorted, w.slots);
+        CHECK_LAUNCH();
+    } else {
+        for (int i = 0; i < 4; ++i)
+            if ((rc = mark())) return rc;
+    }
+    if ((rc = mark())) return rc;  // 5: scans and offsets (with the read-back of the totals)
+    SstLocks none;
+    uint32_t* dput = put_index_out ? static_cast<uint32_t*>(c.lput.p) : nullptr;
+    rc = run_emit(
+        c, none, w, o,
+        [&](uint64_t* dko, uint64_t* dvo, uint8_t* dk, uint8_t* dv) {
+            int r = mark();  // 6: copy
+            if (r) return r;
+            k_mt_copy<<<grid_for(n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(log, w.slots, w.pos, w.totals, dko, dvo, dk,
+                                                                                dv, dput);
+            CHECK_LAUNCH();
+            return int(PBF_OK);
+        },
+        [&] {
+            while (stage < PBF_LOG_SORT_STAGES)  // 7: download (an empty log launched no copy)
+                if (int r = mark()) return r;
+            if (dput && *n_out) HIP_TRY(hipMemcpyAsync(put_index_out, dput, *n_out * 4, hipMemcpyDeviceToHost, s));
+            return int(PBF_OK);
+        });
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c.log_ev[PBF_LOG_SORT_STAGES], s));
+    HIP_TRY(hipEventSynchronize(c.log_ev[PBF_LOG_SORT_STAGES]));
+    for (int i = 0; i < PBF_LOG_SORT_STAGES; ++i) HIP_TRY(hipEventElapsedTime(&c.log_ms[i], c.log_ev[i], c.log_ev[i + 1]));
+    c.log_timed = true;
+    return PBF_OK;
+}
+
+int pbf_log_sort_stage_ms(int device, float* ms_out, uint32_t* merge_passes_out) {
+    if (!ms_out) return fail(PBF_ERR_INVALID, "null pointer");
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    if (!c.log_timed) return fail(PBF_ERR_INVALID, "no completed pbf_log_sort on this device");
+    std::copy(c.log_ms, c.log_ms + PBF_LOG_SORT_STAGES, ms_out);
+    if (merge_passes_out) *merge_passes_out = c.log_passes;
+    return PBF_OK;
 }
 
 }  // extern "C"

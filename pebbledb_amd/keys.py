@@ -193,5 +193,17 @@ class PackedRecords:
         values = np.frombuffer(vb, dtype=np.uint8) if len(vb) else np.zeros(0, np.uint8)
         return cls(keys, values, np.frombuffer(vo, dtype=np.uint64), ascii=bool(ascii))
 
+    @classmethod
+    def from_wal(cls, data) -> "PackedRecords":
+        """Split a write-ahead log — one bytes-like object holding ``Record.to_bytes()`` of every
+        put back to back, as ``WriteAheadLog.read_records`` reads it (src/wal.py:29-31,
+        record.py:93-100) — by from_encoded's rules, in one C loop: the puts in log order,
+        duplicate keys kept.  A stream that ends inside a record raises ValueError with the byte
+        offset of the torn record."""
+        kb, ko, vb, vo, n, ascii, lo, hi = _ingest().pack_wal(data)
+        keys = PackedKeys._from_packed(kb, ko, n, lo, hi)
+        values = np.frombuffer(vb, dtype=np.uint8) if len(vb) else np.zeros(0, np.uint8)
+        return cls(keys, values, np.frombuffer(vo, dtype=np.uint64), ascii=bool(ascii))
+
     def key_str(self, i: int) -> str:
         return self.keys.key(i).decode("utf-8")
