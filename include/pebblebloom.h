@@ -247,6 +247,47 @@ uint32_t pbf_last_probe_detail(pbf_filter_t* f);
 /* How the last tiled build ran: PBF_DETAIL_RING or _SORT [| _PACKED] | (keys per sub-chunk / 256) << 12. */
 uint32_t pbf_last_build_detail(pbf_filter_t* f);
 
+/* What the host planner picks for one tiled build or probe pipeline: the kernel / geometry variant
+ * chosen from (nb_bytes, k, key layout, n, filters per fused probe).  Every field is a uint64_t
+ * (flags are 0 / 1), so the struct has no padding.  When `tiled` is 0 only probe, nf, tiled_ok, tiled,
+ * tb, B and cspace are meaningful. */
+typedef struct pbf_tiled_plan {
+    uint64_t probe, nf;           /* as asked (nf = 1 for a build) */
+    uint64_t tiled_ok;            /* the filter's tile geometry admits the tiled paths at all */
+    uint64_t tiled;               /* ... and so do k, the partition's LDS and (probes) the tile size */
+    uint64_t tb, B, cspace;       /* log2 positions per tile, tiles, m > 2^32 */
+    uint64_t key_mode;            /* 0 fixed 16-byte aligned, 1 fixed length, 2 variable length */
+    uint64_t n;                   /* keys of the pipeline described (the call's last one) */
+    uint64_t pipelines, keys_per_pipeline;
+    uint64_t ring;                /* ring partition: LDS ring entries per tile (0 = counting sort) */
+    uint64_t G, cap, kps, nsub, kpw, nq, scap, spill_cap;  /* PartGeom */
+    uint64_t rounds;              /* multi-filter ring probe: workgroup rounds planned (1..4) */
+    uint64_t pk3;                 /* packed build entries */
+    uint64_t part_kmax;           /* register bucket (or exact k) of the partition kernel */
+    uint64_t exact_k;             /* the partition kernel has k fixed at compile time */
+    uint64_t pow2;                /* ring partition's POW2 branch */
+    uint64_t gsplit, gtq, gather_threads;
+    uint64_t gather_nf;           /* k_gather_ring<1> or <8> */
+    uint64_t lds_part;            /* bytes; the ring partition declares the CU's 160 KiB statically */
+    uint64_t lds_gather, lds_tile;
+    uint64_t tab, tabw, wsh;      /* tile test table mode, TAB 1 chunk words, region shift */
+    uint64_t use_hw;              /* the gather ANDs key words (then hw_is_mask or k_hw_to_hitmask) */
+    uint64_t hw_is_mask;          /* pbf_plan_tiled: assuming a 4-byte aligned mask address */
+} pbf_tiled_plan;
+
+/* The plan for n keys of the given layout (key_len 0 = variable length; keys_16B_aligned matters
+ * for key_len 16 only) against a filter of (nb_bytes, k), nf filters probed together, spare_cu =
+ * a resident one-key reader holds a CU.  Host arithmetic only (no GPU), by the functions the
+ * launches use.  The environment overrides (PBF_PART, PBF_PART_G, PBF_GATHER_SPLIT, PBF_PK3) are
+ * read once per process. */
+int pbf_plan_tiled(uint64_t nb_bytes, uint32_t k, uint32_t key_len, int keys_16B_aligned, uint64_t n, int probe,
+                   uint32_t nf, int spare_cu, pbf_tiled_plan* out);
+/* The plan the filter's last batch build (probe = 0) or batch probe (probe = 1) launched, for the
+ * call's last pipeline, with the call's pipeline count and the real hw_is_mask.  PBF_ERR_INVALID
+ * when there was none or that batch call was not tiled.  One-key probes (pbf_may_contain,
+ * pbf_may_contain_set) run under the handle's lock held shared and leave the report as it is. */
+int pbf_last_tiled_plan(pbf_filter_t* f, int probe, pbf_tiled_plan* out);
+
 /* Release the device's pooled working memory (waits for its last users); the next call
  * re-allocates what it needs.  pbf_scratch_bytes reports what the pool holds now. */
 int pbf_trim(int device);

@@ -71,6 +71,8 @@ SIGNATURES = {
     "pbf_last_probe_mode": (_int, [_vp]),
     "pbf_last_probe_detail": (_u32, [_vp]),
     "pbf_last_build_detail": (_u32, [_vp]),
+    "pbf_plan_tiled": (_int, [_u64, _u32, _u32, _int, _u64, _int, _u32, _int, _vp]),
+    "pbf_last_tiled_plan": (_int, [_vp, _int, _vp]),
     "pbf_may_contain": (_int, [_vp, ctypes.c_char_p, _u64, ctypes.POINTER(_int)]),
     "pbf_may_contain_set": (_int, [_vp, _u32, ctypes.c_char_p, _u64, _u8p]),
     "pbf_trim": (_int, [_int]),
@@ -103,7 +105,37 @@ SIGNATURES = {
     "pbf_source_digest": (ctypes.c_char_p, []),
 }
 
+# pbf_tiled_plan (include/pebblebloom.h): every field a uint64, in the header's order
+TILED_PLAN_FIELDS = (
+    "probe", "nf", "tiled_ok", "tiled", "tb", "B", "cspace", "key_mode", "n", "pipelines", "keys_per_pipeline",
+    "ring", "G", "cap", "kps", "nsub", "kpw", "nq", "scap", "spill_cap", "rounds", "pk3", "part_kmax", "exact_k",
+    "pow2", "gsplit", "gtq", "gather_threads", "gather_nf", "lds_part", "lds_gather", "lds_tile", "tab", "tabw",
+    "wsh", "use_hw", "hw_is_mask")
+
+
+class TiledPlan(ctypes.Structure):
+    _fields_ = [(name, _u64) for name in TILED_PLAN_FIELDS]
+
+    def as_dict(self) -> dict:
+        return {name: int(getattr(self, name)) for name in TILED_PLAN_FIELDS}
+
+
 _lib = None
+
+
+def header_struct_fields(struct: str) -> list[str]:
+    """The field names of `typedef struct <struct> { ... }` in include/pebblebloom.h, in order."""
+    with open(HEADER) as f:
+        text = f.read()
+    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = []
+    for decl in body.split(";"):
+        decl = decl.strip()
+        if decl:
+            assert decl.startswith("uint64_t "), decl
+            names += [x.strip() for x in decl[len("uint64_t "):].split(",")]
+    return names
 
 
 class NativeError(RuntimeError):

@@ -436,12 +436,32 @@ class BloomFilter:
     def last_build_mode(self) -> int:
         return 0 if self._h is None else _native.lib().pbf_last_build_mode(self._h)
 
+    def last_tiled_plan(self, probe: bool) -> dict:
+        """The planner's choices (pbf_tiled_plan as a dict) for the last tiled build (probe=False)
+        or probe (probe=True) of this filter, for the call's last pipeline; ValueError when the
+        last one was not tiled."""
+        out = _native.TiledPlan()
+        _native.check(_native.lib().pbf_last_tiled_plan(self._h, int(bool(probe)), ctypes.byref(out)),
+                      "pbf_last_tiled_plan")
+        return out.as_dict()
+
     @property
     def handle(self):
         return self._h
 
     def __repr__(self):
         return f"BloomFilter(nb_bytes={self.nb_bytes}, nb_hash_functions={self.nb_hash_functions}, device={self.device})"
+
+
+def plan_tiled(nb_bytes: int, k: int, n: int, probe: bool, key_len: int = 16, aligned: bool = True, nf: int = 1,
+               spare_cu: bool = False) -> dict:
+    """What the host planner picks for a tiled build / probe of n keys (pbf_plan_tiled; no GPU).
+    key_len 0 = variable-length keys; `aligned` matters for 16-byte keys only."""
+    out = _native.TiledPlan()
+    _native.check(_native.lib().pbf_plan_tiled(int(nb_bytes), int(k), int(key_len), int(bool(aligned)), int(n),
+                                               int(bool(probe)), int(nf), int(bool(spare_cu)), ctypes.byref(out)),
+                  "pbf_plan_tiled")
+    return out.as_dict()
 
 
 def murmur3(key, seed: int = 0, device: Optional[int] = None) -> int:

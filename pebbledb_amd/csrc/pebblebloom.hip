@@ -278,6 +278,27 @@ uint32_t ceil_log2(uint64_t x) {
     return r;
 }
 
+// Tile geometry of a filter of nb_bytes; *tiled_ok = the tiled paths can serve it.
+TileMap make_tile_map(uint64_t nb_bytes, bool* tiled_ok) {
+    const uint64_t m = nb_bytes * 8;
+    const bool cspace = m > (uint64_t(1) << 32);
+    const uint64_t P = cspace ? (uint64_t(1) << 32) : m;
+    TileMap tm{};
+    tm.im = make_index_map(m);
+    tm.tb = std::min<uint32_t>(20, std::max<uint32_t>(10, ceil_log2(P)));
+    tm.nbuckets = uint32_t((P + (uint64_t(1) << tm.tb) - 1) >> tm.tb);
+    tm.cspace = cspace ? 1 : 0;
+    tm.total_words = (nb_bytes + 3) / 4;
+    *tiled_ok = true;
+    if (cspace) {
+        const uint64_t delta = m - (uint64_t(1) << 32);
+        if (delta % 32) *tiled_ok = false;
+        tm.delta_words = delta / 32;
+    }
+    if (tm.nbuckets > 8192) *tiled_ok = false;  // LDS budget of k_part
+    return tm;
+}
+
 }  // namespace
 
 namespace {
@@ -375,6 +396,7 @@ struct alignas(128) pbf_filter {
     hipEvent_t wait_ev = nullptr;  // pbf_wait_stream: the caller's stream -> this stream
     hipEvent_t sig_ev = nullptr;   // pbf_signal_stream: this stream -> the caller's stream
     const char* last_kernel = "";  // the last kernel enqueued on the stream (wait_stream's report)
+    pbf_tiled_plan last_plan[2] = {};  // [0] the last build, [1] the last probe (tiled = 0: none, or not tiled)
 };
 static_assert(offsetof(pbf_filter, im) + sizeof(IndexMap) <= 128, "per-key fields in the first 128 bytes");
 
@@ -655,6 +677,7 @@ struct PartPlan {
     size_t lds_gather;  // probes: per gather workgroup
     uint32_t gsplit;    // probes: gather splits over tile ranges (grid G x gsplit)
     uint32_t gtq;       // ring gather: quad-table bytes per tile (0 = binary search)
+    uint32_t rounds;    // multi-filter ring probe: rounds of partition workgroups (plan_ring)
 };
 
 // Partition strategy: PBF_PART=sort|ring|sort_build forces one (tests, measurements); default auto.
@@ -746,6 +769,7 @@ PartPlan plan_ring_g(uint32_t B, uint32_t k, uint64_t n, uint32_t kps, bool prob
     const size_t ring_bytes = size_t(ring_lds_words(B)) * 4, spill_entry = probe ? 8 : 4;
     pl.pg.spill_cap = uint32_t(std::min<size_t>(4096, (size_t(kRingLdsWords) * 4 - ring_bytes) / spill_entry));
     pl.lds_part = 0;  // k_part_ring declares the CU's whole LDS statically (kRingLdsWords)
+    pl.rounds = 1;
     set_gather(pl, B, pl.pg.nq + 1, nf);
     return pl;
 }
@@ -766,6 +790,7 @@ PartPlan plan_ring(uint32_t B, uint32_t k, uint64_t n, uint32_t kps, bool probe,
             const PartPlan p2 = plan_ring_g(B, k, n, kps, probe, share, nf, gcap * mult);
             if (p2.pg.G <= pl.pg.G) break;  // (too few keys for more workgroups)
             pl = p2;
+            pl.rounds = uint32_t(mult);
         }
     }
     return pl;
@@ -773,10 +798,8 @@ PartPlan plan_ring(uint32_t B, uint32_t k, uint64_t n, uint32_t kps, bool probe,
 
 // The KMAX of the counting-sort kernel with_part_kernel launches for (k, key layout): the
 // exact-k variants (6, 8, 10) or the register bucket.
-int part_kmax(uint32_t k, int km) {
-    if (km != kFixedN && (k == 6 || k == 8 || k == 10)) return int(k);
-    return kmax_for(k);
-}
+bool part_exact_k(uint32_t k, int km) { return km != kFixedN && (k == 6 || k == 8 || k == 10); }
+int part_kmax(uint32_t k, int km) { return part_exact_k(k, km) ? int(k) : kmax_for(k); }
 
 // Packed build entries (PBF_PK3=0 disables them, for A/B measurements).
 bool pk3_enabled() {
@@ -803,7 +826,8 @@ PartPlan plan_partition(uint32_t B, uint32_t k, int km, uint64_t n, bool probe, 
     const uint64_t kps = kpt * kPartThreads;
     // packed build entries (tiled_kernels.hpp PK3) for the exact-k kernels; their runs are padded
     // (<= 2 pad slots per tile)
-    pl.pk3 = !probe && pk3_enabled() && km != kFixedN && (k == 6 || k == 8 || k == 10);
+    pl.pk3 = !probe && pk3_enabled() && part_exact_k(k, km);
+    pl.rounds = 1;
     const uint64_t need = kps * k + (pl.pk3 ? 2 * std::min<uint64_t>(B, kps * k) : 0);
     uint64_t scap = std::min(need, smax);
     if (pl.pk3) scap -= scap % 3;  // windows hold whole packed words
@@ -867,19 +891,117 @@ PartPlan plan_for(const TileMap& tm, uint32_t k, int km, uint64_t n, bool probe,
     return plan_partition(B, k, km, n, probe, share, probe ? nf : 1, spare);
 }
 
+// LDS of k_tile_build: the tile's words + one fill count per partition workgroup.
+size_t build_tile_lds(const TileMap& tm, const PartGeom& pg) { return ((size_t(1) << tm.tb) / 32 + pg.G) * 4; }
+
+// The tile test of a probe (k_tile_probe / k_tile_probe_set) and what the gather writes.
+struct TileTest {
+    int tab;          // per-word table: 2 = u32 global word index, 1 = u16 region << wsh | word, 0 = binary search
+    uint32_t tabw;    // TAB 1 in chunks of this many table words (0 = the whole table)
+    uint32_t wsh;
+    size_t lds_tile;
+    bool use_hw;      // the gather ANDs key words into hw (several splits or filters)
+};
+
+TileTest plan_tile_test(const TileMap& tm, const PartPlan& pl, uint32_t nf) {
+    const PartGeom& pg = pl.pg;
+    TileTest tt{};
+    tt.use_hw = pl.gsplit > 1 || nf > 1;
+    size_t lds_tile = ((size_t(1) << tm.tb) / 32 + 2 * pg.G + 1 + 16) * 4;
+    // the tile test's per-word table: the u32 global word index per word (TAB 2), else a u16 of
+    // region << wsh | word-in-region (TAB 1: when both fit 16 bits and region * B + tile 24
+    // bits), else a binary search (TAB 0)
+    const uint32_t wpr = pg.cap / 32;
+    const size_t table_words = size_t(pg.G) * wpr;
+    tt.wsh = 32u - uint32_t(__builtin_clz(std::max(wpr, 2u) - 1u));
+    const bool tab1_fits = (uint64_t(pg.G - 1) << tt.wsh) < 65536 && uint64_t(pg.G) * tm.nbuckets < (uint64_t(1) << 24);
+    // TAB 1 in chunks of whole regions when the whole table does not fit beside the tile (at
+    // least one region's words per chunk)
+    const size_t tab1_room = lds_tile < 160 * 1024 ? (160 * 1024 - lds_tile) / 2 & ~size_t(1) : 0;
+    tt.tab = lds_tile + table_words * 4 <= 160 * 1024 ? 2 : (tab1_fits && tab1_room >= wpr ? 1 : 0);
+    tt.tabw = tt.tab == 1 && table_words > tab1_room ? uint32_t(tab1_room) : 0u;
+    lds_tile += tt.tab == 2 ? table_words * 4 : (tt.tab == 1 ? (tt.tabw ? size_t(tt.tabw) : table_words) * 2 : 0);
+    tt.lds_tile = lds_tile;
+    return tt;
+}
+
+// one filter, whole 32-key words, a 4-byte aligned mask: the gather's ANDed words ARE the
+// LSB-first hit mask (bit i of word w = key 32w + i, little-endian), so it ANDs into the
+// caller's mask directly and no conversion kernel runs
+bool hw_is_mask_for(bool use_hw, uint32_t nf, uint64_t n, bool mask_aligned) {
+    return use_hw && nf == 1 && n % 32 == 0 && mask_aligned;
+}
+
+// the set gather: 1024 threads when its LDS admits one workgroup per CU (C5's 8 key bitmaps)
+uint32_t gather_threads_for(uint32_t nf, size_t lds_gather) { return nf > 1 && lds_gather > 80 * 1024 ? 1024 : 512; }
+
+// The ring partition kernel has its seed count fixed at compile time (with_ring_kernel).
+bool ring_exact_k(uint32_t k, int km) { return km != kFixedN && (k == 6 || int(k) == kmax_for(k)); }
+
+// The plan report of one pipeline (pbf_plan_tiled, pbf_last_tiled_plan): the values the launch
+// code itself computed or computes by the same functions.  The caller fills pipelines and
+// keys_per_pipeline.
+pbf_tiled_plan describe_plan(const TileMap& tm, uint32_t k, int km, uint64_t n, bool probe, uint32_t nf,
+                             const PartPlan& pl, bool mask_aligned) {
+    const PartGeom& pg = pl.pg;
+    pbf_tiled_plan o{};
+    o.probe = probe;
+    o.nf = nf;
+    o.tiled_ok = o.tiled = 1;
+    o.tb = tm.tb;
+    o.B = tm.nbuckets;
+    o.cspace = tm.cspace;
+    o.key_mode = uint64_t(km);
+    o.n = n;
+    o.pipelines = 1;
+    o.keys_per_pipeline = n;
+    o.ring = pg.ring;
+    o.G = pg.G;
+    o.cap = pg.cap;
+    o.kps = pg.kps;
+    o.nsub = pg.nsub;
+    o.kpw = pg.kpw;
+    o.nq = pg.nq;
+    o.scap = pg.scap;
+    o.spill_cap = pg.spill_cap;
+    o.rounds = pl.rounds;
+    o.pk3 = pl.pk3;
+    o.part_kmax = uint64_t(pg.ring ? kmax_for(k) : part_kmax(k, km));
+    o.exact_k = pg.ring ? ring_exact_k(k, km) : part_exact_k(k, km);
+    o.pow2 = pg.ring && ring_pow2(tm);
+    o.lds_part = pg.ring ? size_t(kRingLdsWords) * 4 : pl.lds_part;
+    if (probe) {
+        const TileTest tt = plan_tile_test(tm, pl, nf);
+        o.gsplit = pl.gsplit;
+        o.gtq = pl.gtq;
+        o.gather_threads = gather_threads_for(nf, pl.lds_gather);
+        o.gather_nf = nf > 1 ? kMaxProbeSet : 1;
+        o.lds_gather = pl.lds_gather;
+        o.lds_tile = tt.lds_tile;
+        o.tab = uint64_t(tt.tab);
+        o.tabw = tt.tabw;
+        o.wsh = tt.wsh;
+        o.use_hw = tt.use_hw;
+        o.hw_is_mask = hw_is_mask_for(tt.use_hw, nf, n, mask_aligned);
+    } else {
+        o.lds_tile = build_tile_lds(tm, pg);
+    }
+    return o;
+}
+
 // The ring partition kernel for (k, key layout): with the seed count fixed at compile time
 // where it pays (k equal to the register bucket, or k = 6 — C2/C5's k), its k LDS atomics per
 // key issue back to back; other k take the runtime-k kernel of their bucket.
 template <int KX, int KMD, bool PROBE, class L>
 void with_ring_kernel(uint32_t k, bool pow2, L&& launch) {
     if constexpr (KMD != kFixedN) {
-        if constexpr (KX == 8) {
-            if (k == 6) {
-                launch(pow2 ? k_part_ring<6, KMD, PROBE, true, true> : k_part_ring<6, KMD, PROBE, false, true>);
-                return;
+        if (ring_exact_k(k, KMD)) {
+            if constexpr (KX == 8) {
+                if (k == 6) {
+                    launch(pow2 ? k_part_ring<6, KMD, PROBE, true, true> : k_part_ring<6, KMD, PROBE, false, true>);
+                    return;
+                }
             }
-        }
-        if (k == uint32_t(KX)) {
             launch(pow2 ? k_part_ring<KX, KMD, PROBE, true, true> : k_part_ring<KX, KMD, PROBE, false, true>);
             return;
         }
@@ -891,20 +1013,23 @@ void with_ring_kernel(uint32_t k, bool pow2, L&& launch) {
 // configurations use (6: C2/C5 shapes, 8: C3, 10: the fp = 0.001 product sizing of C4 / SSTables).
 template <int KX, int KMD, bool PROBE, class L>
 void with_part_kernel(uint32_t k, L&& launch, bool pk3 = false) {
-    if constexpr (KMD != kFixedN) {
-        if constexpr (KX == 8) {
+    // part_exact_k / part_kmax decide (the plan report reads the same two); every exact k they
+    // name has its instantiation below
+    if (part_exact_k(k, KMD)) {
+        const int kx = part_kmax(k, KMD);
+        if constexpr (KMD != kFixedN && KX == 8) {
             if constexpr (!PROBE) {
-                if (pk3 && k == 6) return launch(k_part<6, KMD, PROBE, true, true>);
-                if (pk3 && k == 8) return launch(k_part<8, KMD, PROBE, true, true>);
+                if (pk3 && kx == 6) return launch(k_part<6, KMD, PROBE, true, true>);
+                if (pk3 && kx == 8) return launch(k_part<8, KMD, PROBE, true, true>);
             }
-            if (k == 6) return launch(k_part<6, KMD, PROBE, true>);
-            if (k == 8) return launch(k_part<8, KMD, PROBE, true>);
+            if (kx == 6) return launch(k_part<6, KMD, PROBE, true>);
+            if (kx == 8) return launch(k_part<8, KMD, PROBE, true>);
         }
-        if constexpr (KX == 16) {
+        if constexpr (KMD != kFixedN && KX == 16) {
             if constexpr (!PROBE) {
-                if (pk3 && k == 10) return launch(k_part<10, KMD, PROBE, true, true>);
+                if (pk3 && kx == 10) return launch(k_part<10, KMD, PROBE, true, true>);
             }
-            if (k == 10) return launch(k_part<10, KMD, PROBE, true>);
+            if (kx == 10) return launch(k_part<10, KMD, PROBE, true>);
         }
     }
     launch(k_part<KX, KMD, PROBE>);
@@ -916,6 +1041,7 @@ int run_tiled(pbf_filter_t* f, const Batch& b) {
     const uint32_t k = f->k;
     const PartPlan pl = plan_for(tm, k, b.km, b.n, false, 1, f->spare_cu);
     const PartGeom& pg = pl.pg;
+    f->last_plan[0] = describe_plan(tm, k, b.km, b.n, false, 1, pl, false);
     // (+ the ring partition's 64-B dummy line per workgroup after the regions)
     HIP_TRY(f->sc->regions.ensure(size_t(pg.G) * B * pg.cap * 4 + size_t(pg.G) * 64));
     HIP_TRY(f->sc->fill.ensure(size_t(pg.G) * B * 4));
@@ -958,7 +1084,7 @@ int run_tiled(pbf_filter_t* f, const Batch& b) {
     });
     HIP_TRY(err);
     LAUNCHED(f, pg.ring ? "k_part_ring<build>" : "k_part<build>");
-    const size_t lds_tile = ((size_t(1) << tm.tb) / 32 + pg.G) * 4;
+    const size_t lds_tile = build_tile_lds(tm, pg);
     if (pl.pk3) {
         HIP_TRY(allow_lds(k_tile_build<true>, lds_tile));
         k_tile_build<true><<<B, 1024, lds_tile, s>>>(tm, pg, regions, fill, f->bitmap, f->pristine ? 1 : 0);
@@ -1005,13 +1131,12 @@ int run_tiled_probe_set(pbf_filter_t* f, pbf_filter_t* const* fs, uint32_t nf, c
     hipStream_t s = f->stream;
     // gather split over S tile ranges (several small workgroups per CU)
     const uint32_t S = pl.gsplit;
-    const bool use_hw = S > 1 || nf > 1;
+    const TileTest tt = plan_tile_test(tm, pl, nf);
+    const bool use_hw = tt.use_hw;
     uint32_t* hw = nullptr;
-    // one filter, whole 32-key words, a 4-byte aligned mask: the gather's ANDed words ARE the
-    // LSB-first hit mask (bit i of word w = key 32w + i, little-endian), so it ANDs into the
-    // caller's mask directly and no conversion kernel runs
-    const bool hw_is_mask = use_hw && nf == 1 && b.n % 32 == 0 &&
-                            (reinterpret_cast<uintptr_t>(hitmasks[0] + hm_off) & 3) == 0;
+    const bool mask_aligned = (reinterpret_cast<uintptr_t>(hitmasks[0] + hm_off) & 3) == 0;
+    const bool hw_is_mask = hw_is_mask_for(use_hw, nf, b.n, mask_aligned);
+    f->last_plan[1] = describe_plan(tm, k, b.km, b.n, true, nf, pl, mask_aligned);
     if (hw_is_mask) {
         hw = reinterpret_cast<uint32_t*>(hitmasks[0] + hm_off);
     } else if (use_hw) {
@@ -1023,21 +1148,10 @@ int run_tiled_probe_set(pbf_filter_t* f, pbf_filter_t* const* fs, uint32_t nf, c
     ps.neg = neg;
     ps.neg_stride = neg_words;
     for (uint32_t i = 0; i < nf; ++i) ps.bm[i] = fs[i]->bitmap;
-    size_t lds_tile = ((size_t(1) << tm.tb) / 32 + 2 * pg.G + 1 + 16) * 4;
-    // the tile test's per-word table: the u32 global word index per word (TAB 2), else a u16 of
-    // region << wsh | word-in-region (TAB 1: when both fit 16 bits and region * B + tile 24
-    // bits), else a binary search (TAB 0)
-    const uint32_t wpr = pg.cap / 32;
-    const size_t table_words = size_t(pg.G) * wpr;
-    const uint32_t wsh = 32u - uint32_t(__builtin_clz(std::max(wpr, 2u) - 1u));
-    const bool tab1_fits = (uint64_t(pg.G - 1) << wsh) < 65536 && uint64_t(pg.G) * B < (uint64_t(1) << 24);
-    // TAB 1 in chunks of whole regions when the whole table does not fit beside the tile (at
-    // least one region's words per chunk)
-    const size_t tab1_room = lds_tile < 160 * 1024 ? (160 * 1024 - lds_tile) / 2 & ~size_t(1) : 0;
-    const int tab = lds_tile + table_words * 4 <= 160 * 1024 ? 2 : (tab1_fits && tab1_room >= wpr ? 1 : 0);
+    const int tab = tt.tab;  // (plan_tile_test)
+    const size_t lds_tile = tt.lds_tile;
     PartGeom tpg = pg;  // (the tile test's copy: tabw)
-    tpg.tabw = tab == 1 && table_words > tab1_room ? uint32_t(tab1_room) : 0u;
-    lds_tile += tab == 2 ? table_words * 4 : (tab == 1 ? (tpg.tabw ? size_t(tpg.tabw) : table_words) * 2 : 0);
+    tpg.tabw = tt.tabw;
     // a region word's global index (region * cap/32 + word) is 32-bit
     if (uint64_t(pg.G) * B * (pg.cap / 32) >= (uint64_t(1) << 32)) return fail(PBF_ERR_INVALID, "probe scratch too large");
     auto tprobe = tab == 2 ? k_tile_probe<2> : (tab == 1 ? k_tile_probe<1> : k_tile_probe<0>);
@@ -1083,8 +1197,7 @@ int run_tiled_probe_set(pbf_filter_t* f, pbf_filter_t* const* fs, uint32_t nf, c
         tprobe_set<<<tgrid, 1024, lds_tile, s>>>(tm, tpg, regions, fill, ps, R, r_words);
     }
     LAUNCHED(f, nf == 1 ? "k_tile_probe" : "k_tile_probe_set");
-    // the set gather: 1024 threads when its LDS admits one workgroup per CU (C5's 8 key bitmaps)
-    const uint32_t gthreads = nf > 1 && pl.lds_gather > 80 * 1024 ? 1024 : 512;
+    const uint32_t gthreads = gather_threads_for(nf, pl.lds_gather);
     gather<<<grid, gthreads, pl.lds_gather, s>>>(tm, pg, b.n, regions, R, fill, pref, neg, hitmasks[0] + hm_off, hw, nf,
                                            r_words, neg_words, pl.gtq);
     LAUNCHED(f, "k_gather_ring");
@@ -1109,8 +1222,14 @@ bool part_fits(uint32_t B, uint32_t k, bool probe) {
     return size_t(3 * B + 17) * 4 + size_t(kPartThreads) * k * (probe ? 6 : 4) <= 156 * 1024;
 }
 
+// The tiled build (probe) exists for this geometry and k at all (k == 0 launches nothing and is
+// left to the callers).
+bool tiled_admits(bool tiled_ok, const TileMap& tm, uint32_t k, bool probe) {
+    return tiled_ok && k <= 32 && (!probe || tm.tb <= kSlotShift) && part_fits(tm.nbuckets, k, probe);
+}
+
 bool want_tiled(pbf_filter_t* f, uint64_t n) {
-    if (!f->tiled_ok || f->k == 0 || f->k > 32 || !part_fits(f->tm.nbuckets, f->k, false)) return false;
+    if (f->k == 0 || !tiled_admits(f->tiled_ok, f->tm, f->k, false)) return false;
     if (f->mode == PBF_BUILD_TILED) return true;
     if (f->mode == PBF_BUILD_ATOMIC) return false;
     const uint64_t npos = n * f->k;
@@ -1121,8 +1240,7 @@ bool want_tiled(pbf_filter_t* f, uint64_t n) {
 }
 
 bool want_tiled_probe(pbf_filter_t* f, uint64_t n) {
-    if (!f->tiled_ok || f->k == 0 || f->k > 32 || f->tm.tb > kSlotShift || !part_fits(f->tm.nbuckets, f->k, true))
-        return false;
+    if (f->k == 0 || !tiled_admits(f->tiled_ok, f->tm, f->k, true)) return false;
     if (f->probe_mode == PBF_PROBE_TILED) return true;
     if (f->probe_mode == PBF_PROBE_DIRECT) return false;
     // direct: ~1..k random 64-B requests per key, cheap while the bitmap stays in one XCD's
@@ -1138,13 +1256,12 @@ bool want_tiled_probe(pbf_filter_t* f, uint64_t n) {
 // workgroup fits the LDS (halving, then a search between the last two sizes in 64Ki-key steps),
 // then the batch split into equal pipelines (C5's 100M keys: 3 x 33.3M instead of 4 x 22.4M +
 // 10.4M — every pipeline streams the filters' bitmaps once, however few keys it holds).
-uint64_t tiled_probe_batch(pbf_filter_t* f, int km, uint32_t nf, uint64_t total) {
-    const uint32_t k = f->k;
+uint64_t tiled_probe_batch(const TileMap& tm, uint32_t k, int km, uint32_t nf, uint64_t total, bool spare) {
     auto fits = [&](uint64_t m) {
-        const PartPlan pl = plan_for(f->tm, k, km, m, true, nf, f->spare_cu);
+        const PartPlan pl = plan_for(tm, k, km, m, true, nf, spare);
         // the tile test addresses a region word by a u32 global index (run_tiled_probe_set)
         return pl.lds_gather <= 156 * 1024 && pl.pg.cap <= 65535 &&
-               uint64_t(pl.pg.G) * f->tm.nbuckets * (pl.pg.cap / 32) < (uint64_t(1) << 32);
+               uint64_t(pl.pg.G) * tm.nbuckets * (pl.pg.cap / 32) < (uint64_t(1) << 32);
     };
     const uint64_t top = std::max<uint64_t>(64, (kMaxProbePositions / k) & ~uint64_t(63));
     uint64_t n = top;
@@ -1165,23 +1282,35 @@ uint64_t tiled_probe_batch(pbf_filter_t* f, int km, uint32_t nf, uint64_t total)
     return n;
 }
 
+// Keys per tiled-build pipeline: positions are counted in u32 inside one pipeline, and a region
+// holds < 2^24 entries (the partitions' 24-bit region addressing): very large inputs are batched.
+uint64_t tiled_build_batch(const TileMap& tm, uint32_t k) {
+    const double share = busiest_tile_share(tm);
+    const double cap_keys = double((1u << 24) - 64) * part_max_groups(false) / (double(k) * share * 1.25);
+    return std::max<uint64_t>(1, std::min<uint64_t>(kMaxPositions / k, uint64_t(cap_keys)));
+}
+
+// The call's pipeline count in the report of its last pipeline.
+void note_pipelines(pbf_tiled_plan& p, uint64_t n, uint64_t per) {
+    p.pipelines = (n + per - 1) / per;
+    p.keys_per_pipeline = std::min(n, per);
+}
+
 int add_device(pbf_filter_t* f, const Batch& b) {
     if (b.n == 0 || f->k == 0) return PBF_OK;
     if (want_tiled(f, b.n)) {
         f->spare_cu = resident_live(f->device);
-        // positions are counted in u32 inside one pipeline, and a region holds < 2^24 entries
-        // (the partitions' 24-bit region addressing): batch very large inputs
-        const double share = busiest_tile_share(f->tm);
-        const double cap_keys = double((1u << 24) - 64) * part_max_groups(false) / (double(f->k) * share * 1.25);
-        const uint64_t per = std::max<uint64_t>(1, std::min<uint64_t>(kMaxPositions / f->k, uint64_t(cap_keys)));
+        const uint64_t per = tiled_build_batch(f->tm, f->k);
         for (uint64_t i0 = 0; i0 < b.n; i0 += per) {
             int rc = run_tiled(f, slice(b, i0, std::min<uint64_t>(per, b.n - i0)));
             if (rc) return rc;
         }
+        note_pipelines(f->last_plan[0], b.n, per);
         f->last_mode = PBF_BUILD_TILED;
         return PBF_OK;
     }
     f->last_mode = PBF_BUILD_ATOMIC;
+    f->last_plan[0].tiled = 0;
     return run_atomic(f, b);
 }
 
@@ -1191,12 +1320,13 @@ int probe_device(pbf_filter_t* f, const Batch& b, uint8_t* hitmask_dev) {
     if (rc) return rc;
     if (want_tiled_probe(f, b.n)) {
         f->spare_cu = resident_live(f->device);
-        const uint64_t per = tiled_probe_batch(f, b.km, 1, b.n);
+        const uint64_t per = tiled_probe_batch(f->tm, f->k, b.km, 1, b.n, f->spare_cu);
         for (uint64_t i0 = 0; i0 < b.n; i0 += per) {
             rc = run_tiled_probe(f, slice(b, i0, std::min<uint64_t>(per, b.n - i0)), hitmask_dev + i0 / 8);
             if (rc) return rc;
         }
         f->last_probe_detail |= uint32_t(std::min<uint64_t>((b.n + per - 1) / per, 4095)) << 16;
+        note_pipelines(f->last_plan[1], b.n, per);
         f->last_probe_mode = PBF_PROBE_TILED;
         return PBF_OK;
     }
@@ -1208,6 +1338,7 @@ int probe_device(pbf_filter_t* f, const Batch& b, uint8_t* hitmask_dev) {
     LAUNCHED(f, "k_probe");
     f->last_probe_mode = PBF_PROBE_DIRECT;
     f->last_probe_detail = 0;
+    f->last_plan[1].tiled = 0;
     return PBF_OK;
 }
 
@@ -1299,6 +1430,7 @@ int probe_set_direct(pbf_filter_t* f0, std::vector<pbf_filter_t*>& grp, std::vec
     for (pbf_filter_t* f : grp) {
         f->last_probe_mode = PBF_PROBE_DIRECT;
         f->last_probe_detail = PBF_DETAIL_SET | (uint32_t(std::min<size_t>(grp.size(), kMaxFilterSet)) << 8);
+        f->last_plan[1].tiled = 0;
     }
     return PBF_OK;
 }
@@ -1328,7 +1460,7 @@ int probe_multi_device(pbf_filter_t* const* fs, uint32_t nf, const Batch& b, uin
     }
     if (shared_probe(fs, nf, b.n)) {
         f0->spare_cu = resident_live(f0->device);
-        const uint64_t per = tiled_probe_batch(f0, b.km, std::min<uint32_t>(nf, kMaxProbeSet), b.n);
+        const uint64_t per = tiled_probe_batch(f0->tm, f0->k, b.km, std::min<uint32_t>(nf, kMaxProbeSet), b.n, f0->spare_cu);
         for (uint64_t i0 = 0; i0 < b.n; i0 += per) {
             const Batch c = slice(b, i0, std::min<uint64_t>(per, b.n - i0));
             for (uint32_t g0 = 0; g0 < nf; g0 += kMaxProbeSet) {
@@ -1338,9 +1470,11 @@ int probe_multi_device(pbf_filter_t* const* fs, uint32_t nf, const Batch& b, uin
             }
         }
         f0->last_probe_detail |= uint32_t(std::min<uint64_t>((b.n + per - 1) / per, 4095)) << 16;
+        note_pipelines(f0->last_plan[1], b.n, per);
         for (uint32_t i = 0; i < nf; ++i) {
             fs[i]->last_probe_mode = PBF_PROBE_TILED;
             fs[i]->last_probe_detail = f0->last_probe_detail.load();
+            if (i) fs[i]->last_plan[1] = f0->last_plan[1];
         }
     } else {
         // direct groups by k (in first-appearance order), then the per-filter pipelines
@@ -2560,24 +2694,9 @@ int pbf_create(int device, uint64_t nb_bytes, uint32_t nb_hash_functions, pbf_fi
     f->k = nb_hash_functions;
     f->words = (nb_bytes + 3) / 4;
     f->alloc_words = (f->words + 3) & ~uint64_t(3);
-    const uint64_t m = nb_bytes * 8;
-    f->im = make_index_map(m);
-    // tile geometry
-    const bool cspace = m > (uint64_t(1) << 32);
-    const uint64_t P = cspace ? (uint64_t(1) << 32) : m;
-    TileMap tm{};
-    tm.im = f->im;
-    tm.tb = std::min<uint32_t>(20, std::max<uint32_t>(10, ceil_log2(P)));
-    tm.nbuckets = uint32_t((P + (uint64_t(1) << tm.tb) - 1) >> tm.tb);
-    tm.cspace = cspace ? 1 : 0;
-    tm.total_words = f->words;
-    f->tiled_ok = true;
-    if (cspace) {
-        const uint64_t delta = m - (uint64_t(1) << 32);
-        if (delta % 32) f->tiled_ok = false;
-        tm.delta_words = delta / 32;
-    }
-    if (tm.nbuckets > 8192) f->tiled_ok = false;  // LDS budget of k_part
+    const TileMap tm = make_tile_map(nb_bytes, &f->tiled_ok);
+    const bool cspace = tm.cspace != 0;
+    f->im = tm.im;
     f->tm = tm;
     hipError_t e = pooled_stream(device, &f->stream);
     if (e == hipSuccess) {
@@ -3132,7 +3251,7 @@ void* pbf_device_bitmap(pbf_filter_t* f) {
 int pbf_set_build_mode(pbf_filter_t* f, int mode) {
     LOCK(f);
     if (mode < PBF_BUILD_AUTO || mode > PBF_BUILD_TILED) return fail(PBF_ERR_INVALID, "bad build mode");
-    if (mode == PBF_BUILD_TILED && (!f->tiled_ok || f->k > 32 || !part_fits(f->tm.nbuckets, f->k, false)))
+    if (mode == PBF_BUILD_TILED && !tiled_admits(f->tiled_ok, f->tm, f->k, false))
         return fail(PBF_ERR_INVALID, "tiled build unsupported for this m / k");
     f->mode = mode;
     return PBF_OK;
@@ -3143,8 +3262,7 @@ int pbf_last_build_mode(pbf_filter_t* f) { return f ? f->last_mode : 0; }
 int pbf_set_probe_mode(pbf_filter_t* f, int mode) {
     LOCK(f);
     if (mode < PBF_PROBE_AUTO || mode > PBF_PROBE_TILED) return fail(PBF_ERR_INVALID, "bad probe mode");
-    if (mode == PBF_PROBE_TILED &&
-        (!f->tiled_ok || f->k > 32 || f->tm.tb > kSlotShift || !part_fits(f->tm.nbuckets, f->k, true)))
+    if (mode == PBF_PROBE_TILED && !tiled_admits(f->tiled_ok, f->tm, f->k, true))
         return fail(PBF_ERR_INVALID, "tiled probe unsupported for this m / k");
     f->probe_mode = mode;
     return PBF_OK;
@@ -3153,6 +3271,44 @@ int pbf_set_probe_mode(pbf_filter_t* f, int mode) {
 int pbf_last_probe_mode(pbf_filter_t* f) { return f ? f->last_probe_mode.load() : 0; }
 uint32_t pbf_last_probe_detail(pbf_filter_t* f) { return f ? f->last_probe_detail.load() : 0u; }
 uint32_t pbf_last_build_detail(pbf_filter_t* f) { return f ? f->last_build_detail : 0; }
+
+int pbf_plan_tiled(uint64_t nb_bytes, uint32_t k, uint32_t key_len, int keys_16B_aligned, uint64_t n, int probe,
+                   uint32_t nf, int spare_cu, pbf_tiled_plan* out) {
+    if (!out) return fail(PBF_ERR_INVALID, "null out");
+    if (nb_bytes == 0) return fail(PBF_ERR_ZERO_SIZE, "nb_bytes == 0 (integer modulo by zero)");
+    if (n == 0 || nf == 0 || nf > uint32_t(kMaxProbeSet) || (!probe && nf != 1))
+        return fail(PBF_ERR_INVALID, "pbf_plan_tiled: n >= 1, 1 <= nf <= 8 (1 for a build)");
+    bool tiled_ok = false;
+    const TileMap tm = make_tile_map(nb_bytes, &tiled_ok);
+    const int km = key_len == 0 ? kVar : (key_len == 16 && keys_16B_aligned ? kFixed16 : kFixedN);
+    const bool pr = probe != 0, spare = spare_cu != 0;
+    if (k == 0 || !tiled_admits(tiled_ok, tm, k, pr)) {
+        pbf_tiled_plan o{};
+        o.probe = pr;
+        o.nf = nf;
+        o.tiled_ok = tiled_ok;
+        o.tb = tm.tb;
+        o.B = tm.nbuckets;
+        o.cspace = tm.cspace;
+        *out = o;
+        return PBF_OK;
+    }
+    // the call's pipelines as add_device / probe_device split them; the last one is described
+    const uint64_t per = pr ? tiled_probe_batch(tm, k, km, nf, n, spare) : tiled_build_batch(tm, k);
+    const uint64_t last = n - (n - 1) / per * per;
+    *out = describe_plan(tm, k, km, last, pr, nf, plan_for(tm, k, km, last, pr, nf, spare), true);
+    note_pipelines(*out, n, per);
+    return PBF_OK;
+}
+
+int pbf_last_tiled_plan(pbf_filter_t* f, int probe, pbf_tiled_plan* out) {
+    if (!f || !out) return fail(PBF_ERR_INVALID, "null filter handle or out");
+    LOCK(f);
+    const pbf_tiled_plan& p = f->last_plan[probe ? 1 : 0];
+    if (!p.tiled) return fail(PBF_ERR_INVALID, "no tiled plan: the last batch build / probe was not tiled");
+    *out = p;
+    return PBF_OK;
+}
 
 int pbf_encode_data_blocks(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
                            const uint64_t* value_offsets, uint64_t n, const uint64_t* block_first,

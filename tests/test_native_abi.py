@@ -16,6 +16,12 @@ def test_header_declares_expected_functions():
     assert set(names) == set(_native.SIGNATURES), set(names) ^ set(_native.SIGNATURES)
 
 
+def test_tiled_plan_struct_matches_the_header():
+    """_native.TiledPlan mirrors pbf_tiled_plan field for field (all uint64, the header's order)."""
+    assert _native.header_struct_fields("pbf_tiled_plan") == list(_native.TILED_PLAN_FIELDS)
+    assert ctypes.sizeof(_native.TiledPlan) == 8 * len(_native.TILED_PLAN_FIELDS)
+
+
 def test_library_loads_and_exports_every_header_symbol():
     L = _native.lib()
     for name in _native.header_functions():
