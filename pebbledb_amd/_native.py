@@ -99,6 +99,17 @@ SIGNATURES = {
     "pbf_log_sort": (_int, [_int, _u8p, _vp, _u8p, _vp, _u64, _u8p, _u64, _vp, _u8p, _u64, _vp, _u64, _vp,
                             ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "pbf_log_sort_stage_ms": (_int, [_int, _vp, ctypes.POINTER(_u32)]),
+    "pbf_plan_device": (_int, [_int, _vp, _vp, _vp, _u64, _u64, _u64, _vp, _vp, _vp, _u64, ctypes.POINTER(_u64),
+                               ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "pbf_compact_begin": (_int, [_vp, _u32, _int, _u64, _u64, ctypes.POINTER(_vp), ctypes.POINTER(_u64),
+                                 ctypes.POINTER(_u64)]),
+    "pbf_flush_begin": (_int, [_int, _u8p, _vp, _u8p, _vp, _u64, _u64, ctypes.POINTER(_vp)]),
+    "pbf_job_table_info": (_int, [_vp, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                  ctypes.POINTER(_u64)]),
+    "pbf_job_finish": (_int, [_vp, _vp, _vp, _u8p, _vp, _vp]),
+    "pbf_job_abort": (_int, [_vp]),
+    "pbf_job_stage_ms": (_int, [_int, _vp]),
+    "pbf_sst_read_data": (_int, [_vp, _u8p, _u64]),
     "pbf_gen_splitmix_hex": (_int, [_int, _vp, _u8p, _u64, _u64, _u64]),
     "pbf_gen_varlen": (_int, [_int, _vp, _u8p, _vp, _u64, _u64, _u64]),
     "pbf_last_error": (ctypes.c_char_p, []),

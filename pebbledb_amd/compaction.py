@@ -18,7 +18,9 @@ table can hold (``DeviceSSTable`` refuses the non-ASCII keys the reference canno
 
 ``compact_l0`` / ``compact_level`` are the merge / concatenation followed by
 ``sstable_data.build_sstables``: the files ``_compact`` writes, without the state update and the
-manifest event, which stay with the caller.
+manifest event, which stay with the caller.  ``compact_l0_resident`` / ``compact_level_resident``
+are the same compactions with the run kept on the device and the outputs opened there as
+``DeviceSSTable``s (``resident_write``; include/pebblebloom.h "Resident write path").
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ import numpy as np
 
 from . import _native
 from .keys import PackedKeys, PackedRecords
-from .sstable_data import BLOCK_SIZE, build_sstables
+from .sstable_data import BLOCK_SIZE, _check_block_size, _check_max_sstable_size, build_sstables
 from .sstable_read import _handles
 
 _vp = ctypes.c_void_p
@@ -125,3 +127,34 @@ def compact_level(tables: Sequence, max_sstable_size: int = 262_144_000, block_s
     tables = list(tables)
     run = concat_tables(tables)
     return build_sstables(run, None, max_sstable_size, block_size, fp_rate, tables[0].device if device is None else device)
+
+
+def _compact_resident(tables, mode: int, max_sstable_size: int, block_size: int, fp_rate: float):
+    from .resident_write import finish_job
+
+    tables = _table_list(tables, "merge")
+    _check_block_size(block_size)
+    _check_max_sstable_size(max_sstable_size)
+    hs = _handles(tables)
+    job, nt, written = _vp(), ctypes.c_uint64(), ctypes.c_uint64()
+    _native.check(_native.lib().pbf_compact_begin(hs, len(tables), mode, block_size, max_sstable_size,
+                                                  ctypes.byref(job), ctypes.byref(nt), ctypes.byref(written)),
+                  "pbf_compact_begin")
+    return finish_job(job, nt.value, fp_rate, tables[0].device), written.value
+
+
+def compact_l0_resident(tables: Sequence, max_sstable_size: int = 262_144_000, block_size: int = BLOCK_SIZE,
+                        fp_rate: float = 0.001):
+    """``compact_l0`` without the host: the merged run stays on the device, where it is planned
+    (csrc/sstable_plan_kernels.hpp), encoded, filtered and opened.  Returns (outputs as
+    ``DeviceSSTable``s in the order ``_compact`` returns them, records written); each output's
+    ``to_bytes()`` is the file ``compact_l0`` returns for it.  Arguments and refusals are
+    ``compact_l0``'s; no output gives ``([], written)``.  The inputs may be closed as soon as the
+    call returns."""
+    return _compact_resident(tables, _native.PBF_MERGE_DEDUP, max_sstable_size, block_size, fp_rate)
+
+
+def compact_level_resident(tables: Sequence, max_sstable_size: int = 262_144_000, block_size: int = BLOCK_SIZE,
+                           fp_rate: float = 0.001):
+    """``compact_level`` without the host, as ``compact_l0_resident``."""
+    return _compact_resident(tables, _native.PBF_MERGE_CONCAT, max_sstable_size, block_size, fp_rate)

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <mutex>
 #include <set>
@@ -31,6 +32,7 @@
 #include "tiled_kernels.hpp"
 #include "ring_kernels.hpp"
 #include "sstable_kernels.hpp"
+#include "sstable_plan_kernels.hpp"
 #include "lsm_kernels.hpp"
 #include "set_kernels.hpp"
 #include "reader_service.hpp"
@@ -3855,6 +3857,50 @@ void sst_free(pbf_sstable_t* t) {
     t->rec_base.release();
 }
 
+// The validator over the data sections of nt new tables on s (k_sst_validate per table, then the
+// seams between blocks on every index that came out whole): fills each table's index and prefixes
+// and r[t], its report.  offs[t] = the table's nblocks + 1 block offsets in device memory, rep_dev
+// = nt reports of device memory.  Returns once the reports are read back.
+int sst_index_tables(hipStream_t s, pbf_sstable_t* const* ts, const uint32_t* const* offs, uint32_t nt,
+                     SstReport* rep_dev, SstReport* r) {
+    HIP_TRY(hipMemsetAsync(rep_dev, 0, sizeof(SstReport) * nt, s));
+    for (uint32_t t = 0; t < nt; ++t) {
+        k_sst_validate<<<ts[t]->nblocks, 256, 0, s>>>(static_cast<const uint8_t*>(ts[t]->data.p), offs[t], ts[t]->nblocks,
+                                                      static_cast<SstBlock*>(ts[t]->index.p),
+                                                      static_cast<uint64_t*>(ts[t]->prefix.p), rep_dev + t);
+        CHECK_LAUNCH();
+    }
+    HIP_TRY(hipMemcpyAsync(r, rep_dev, sizeof(SstReport) * nt, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    bool seams = false;
+    for (uint32_t t = 0; t < nt; ++t) {
+        if (r[t].rules || ts[t]->nblocks < 2) continue;  // the seams between blocks, on an index that is whole
+        k_sst_validate_seams<<<grid_for(ts[t]->nblocks - 1, 256, 1u << 23), 256, 0, s>>>(
+            static_cast<const uint8_t*>(ts[t]->data.p), static_cast<const SstBlock*>(ts[t]->index.p), ts[t]->nblocks,
+            rep_dev + t);
+        CHECK_LAUNCH();
+        seams = true;
+    }
+    if (seams) {
+        HIP_TRY(hipMemcpyAsync(r, rep_dev, sizeof(SstReport) * nt, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return PBF_OK;
+}
+
+bool sst_report_bad(const SstReport& r) { return r.rules || r.bad_blocks || r.bad_records || r.order_violations; }
+
+int sst_refuse(const SstReport& r) {
+    return fail(PBF_ERR_INVALID, "SSTable refused (" + std::to_string(r.bad_blocks) + " bad blocks, " +
+                                     std::to_string(r.bad_records) + " bad records, " +
+                                     std::to_string(r.order_violations) + " order violations): " + sst_rule_names(r.rules));
+}
+
+void sst_register(pbf_sstable_t* t) {
+    std::unique_lock<std::shared_mutex> reg(g_sst_mu);
+    g_sst_live.insert(t);
+}
+
 }  // namespace
 
 extern "C" {
@@ -3901,33 +3947,13 @@ int pbf_sst_open(int device, const uint8_t* data, uint64_t data_len, const uint3
     SST_TRY(hipMemcpyAsync(t->data.p, data, data_len, data_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     SST_TRY(hipMemsetAsync(static_cast<uint8_t*>(t->data.p) + data_len, 0, 16, s));
     SST_TRY(hipMemcpyAsync(c.offs.p, block_off, (size_t(nblocks) + 1) * 4, hipMemcpyHostToDevice, s));
-    SST_TRY(hipMemsetAsync(c.rep.p, 0, sizeof(SstReport), s));
-    auto* d = static_cast<const uint8_t*>(t->data.p);
-    auto* idx = static_cast<SstBlock*>(t->index.p);
-    auto* rep = static_cast<SstReport*>(c.rep.p);
-    k_sst_validate<<<nblocks, 256, 0, s>>>(d, static_cast<const uint32_t*>(c.offs.p), nblocks, idx,
-                                           static_cast<uint64_t*>(t->prefix.p), rep);
-    SST_TRY(hipGetLastError());
-    SstReport r{};
-    SST_TRY(hipMemcpyAsync(&r, rep, sizeof r, hipMemcpyDeviceToHost, s));
-    SST_TRY(hipStreamSynchronize(s));
-    if (!r.rules && nblocks > 1) {  // the seams between blocks, on an index that is whole
-        k_sst_validate_seams<<<grid_for(nblocks - 1, 256, 1u << 23), 256, 0, s>>>(d, idx, nblocks, rep);
-        SST_TRY(hipGetLastError());
-        SST_TRY(hipMemcpyAsync(&r, rep, sizeof r, hipMemcpyDeviceToHost, s));
-        SST_TRY(hipStreamSynchronize(s));
-    }
 #undef SST_TRY
-    if (r.rules || r.bad_blocks || r.bad_records || r.order_violations)
-        return bail(fail(PBF_ERR_INVALID, "SSTable refused (" + std::to_string(r.bad_blocks) + " bad blocks, " +
-                                              std::to_string(r.bad_records) + " bad records, " +
-                                              std::to_string(r.order_violations) + " order violations): " +
-                                              sst_rule_names(r.rules)));
+    SstReport r{};
+    const uint32_t* offs = static_cast<const uint32_t*>(c.offs.p);
+    if ((rc = sst_index_tables(s, &t, &offs, 1, static_cast<SstReport*>(c.rep.p), &r))) return bail(rc);
+    if (sst_report_bad(r)) return bail(sst_refuse(r));
     t->nrecords = r.records;
-    {
-        std::unique_lock<std::shared_mutex> reg(g_sst_mu);
-        g_sst_live.insert(t);
-    }
+    sst_register(t);
     *out = t;
     return PBF_OK;
 }
@@ -4200,6 +4226,9 @@ struct RunOut {
     uint64_t *n, *key_bytes, *value_bytes;  // the run's totals, written even where it does not fit
     int on_device;
     hipStream_t s;
+    // device form only: called once the totals are known (n records, key bytes, value bytes) to
+    // provide the four output buffers and their capacities in `o`, before the capacities are checked
+    std::function<int(uint64_t, uint64_t, uint64_t, RunOut&)> alloc;
 };
 
 // The context's working memory for a run over n ranked input records.
@@ -4247,7 +4276,8 @@ int run_prepare(SstCtx& c, const RunOut& o, uint64_t n, RunWork& w) {
 // still its own.  Then the device form records merge_done and the tables' use; the host form
 // copies the run back and waits.  An empty run (n == 0) is the two offsets arrays {0}.
 template <class Copy, class Extra>
-int run_emit(SstCtx& c, SstLocks& locks, const RunWork& w, const RunOut& o, Copy copy, Extra extra) {
+int run_emit(SstCtx& c, SstLocks& locks, const RunWork& w, const RunOut& o_in, Copy copy, Extra extra) {
+    RunOut o = o_in;
     hipStream_t s = o.s;
     uint64_t tot[kMergeTotals] = {0, 0, 0};
     if (w.n) {
@@ -4261,6 +4291,10 @@ int run_emit(SstCtx& c, SstLocks& locks, const RunWork& w, const RunOut& o, Copy
     *o.n = tot[0];
     *o.key_bytes = tot[1];
     *o.value_bytes = tot[2];
+    if (o.alloc) {
+        int rc = o.alloc(tot[0], tot[1], tot[2], o);
+        if (rc) return rc;
+    }
     if (tot[0] + 1 > o.offsets_cap)
         return fail(PBF_ERR_INVALID, "the run holds " + std::to_string(tot[0]) + " records: each offsets array needs " +
                                          std::to_string(tot[0] + 1) + " entries, offsets_cap is " +
@@ -4307,19 +4341,11 @@ int run_emit(SstCtx& c, SstLocks& locks, const RunWork& w, const RunOut& o, Copy
     return PBF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint8_t* keys_out, uint64_t keys_cap,
-                  uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
-                  uint64_t offsets_cap, uint64_t* n_out, uint64_t* key_bytes_out, uint64_t* value_bytes_out,
-                  int on_device, void* stream) {
+// pbf_sst_merge into `o`; ctx_stream: on the context's stream (o.s is set here), else on o.s.
+int sst_merge_run(pbf_sstable_t* const* tables, uint32_t ntables, int mode, RunOut o, bool ctx_stream) {
     int rc = check_run_tables(tables, ntables, "merge");
     if (rc) return rc;
     if (mode != PBF_MERGE_DEDUP && mode != PBF_MERGE_CONCAT) return fail(PBF_ERR_INVALID, "unknown merge mode");
-    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out)
-        return fail(PBF_ERR_INVALID, "null pointer");
     SstLocks locks;
     if ((rc = locks.take(tables, ntables))) return rc;
     const int device = tables[0]->device;
@@ -4332,14 +4358,33 @@ int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint
     std::lock_guard<std::mutex> lock(c.mu);
     if ((rc = sst_ctx_stream(c, device))) return rc;
     if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
-    hipStream_t s = on_device ? static_cast<hipStream_t>(stream) : c.stream;
-    const RunOut o{keys_out, keys_cap, key_offsets_out, values_out, values_cap, value_offsets_out, offsets_cap,
-                   n_out, key_bytes_out, value_bytes_out, on_device, s};
+    if (ctx_stream) o.s = c.stream;
+    hipStream_t s = o.s;
     RunWork w;
     if ((rc = run_prepare(c, o, n, w))) return rc;
     k_merge_rank<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(set, n, mode == PBF_MERGE_DEDUP, w.slots);
     CHECK_LAUNCH();
     return run_emit(c, locks, w, o, merge_copy_launch(set, w, s), [] { return int(PBF_OK); });
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbf_sst_merge(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint8_t* keys_out, uint64_t keys_cap,
+                  uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
+                  uint64_t offsets_cap, uint64_t* n_out, uint64_t* key_bytes_out, uint64_t* value_bytes_out,
+                  int on_device, void* stream) {
+    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out) {
+        int rc = check_run_tables(tables, ntables, "merge");  // (the table list is judged first)
+        if (rc) return rc;
+        if (mode != PBF_MERGE_DEDUP && mode != PBF_MERGE_CONCAT) return fail(PBF_ERR_INVALID, "unknown merge mode");
+        return fail(PBF_ERR_INVALID, "null pointer");
+    }
+    return sst_merge_run(tables, ntables, mode,
+                         RunOut{keys_out, keys_cap, key_offsets_out, values_out, values_cap, value_offsets_out, offsets_cap,
+                                n_out, key_bytes_out, value_bytes_out, on_device, static_cast<hipStream_t>(stream), {}},
+                         !on_device);
 }
 
 }  // extern "C"
@@ -4552,17 +4597,11 @@ int check_log_offsets(const uint64_t* o, uint64_t n, const char* what) {
     return PBF_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pbf_log_sort(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
-                 const uint64_t* value_offsets, uint64_t n, uint8_t* keys_out, uint64_t keys_cap,
-                 uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
-                 uint64_t offsets_cap, uint32_t* put_index_out, uint64_t* n_out, uint64_t* key_bytes_out,
-                 uint64_t* value_bytes_out) {
-    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out)
-        return fail(PBF_ERR_INVALID, "null pointer");
+// pbf_log_sort into `o` (host form, or device form: the run stays in the buffers o.alloc provides),
+// on the context's stream; the run is complete on return in both forms.
+int log_sort_run(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
+                 const uint64_t* value_offsets, uint64_t n, RunOut o, uint32_t* put_index_out) {
+    uint64_t* const n_out = o.n;
     if (n >= 0xFFFFFFFFull) return fail(PBF_ERR_INVALID, "a put log holds fewer than 2^32 - 1 puts, got " + std::to_string(n));
     int rc;
     if (n) {
@@ -4587,8 +4626,7 @@ int pbf_log_sort(int device, const uint8_t* keys, const uint64_t* key_offsets, c
         HIP_TRY(hipEventRecord(c.log_ev[stage++], s));
         return PBF_OK;
     };
-    const RunOut o{keys_out, keys_cap, key_offsets_out, values_out, values_cap, value_offsets_out, offsets_cap,
-                   n_out, key_bytes_out, value_bytes_out, 0, s};
+    o.s = s;
     RunWork w;
     if ((rc = run_prepare(c, o, n, w))) return rc;
     MtLog log{};
@@ -4658,6 +4696,23 @@ int pbf_log_sort(int device, const uint8_t* keys, const uint64_t* key_offsets, c
     return PBF_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int pbf_log_sort(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
+                 const uint64_t* value_offsets, uint64_t n, uint8_t* keys_out, uint64_t keys_cap,
+                 uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
+                 uint64_t offsets_cap, uint32_t* put_index_out, uint64_t* n_out, uint64_t* key_bytes_out,
+                 uint64_t* value_bytes_out) {
+    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out)
+        return fail(PBF_ERR_INVALID, "null pointer");
+    return log_sort_run(device, keys, key_offsets, values, value_offsets, n,
+                        RunOut{keys_out, keys_cap, key_offsets_out, values_out, values_cap, value_offsets_out, offsets_cap,
+                               n_out, key_bytes_out, value_bytes_out, 0, nullptr, {}},
+                        put_index_out);
+}
+
 int pbf_log_sort_stage_ms(int device, float* ms_out, uint32_t* merge_passes_out) {
     if (!ms_out) return fail(PBF_ERR_INVALID, "null pointer");
     SstCtx& c = sst_ctx(device);
@@ -4665,6 +4720,485 @@ int pbf_log_sort_stage_ms(int device, float* ms_out, uint32_t* merge_passes_out)
     if (!c.log_timed) return fail(PBF_ERR_INVALID, "no completed pbf_log_sort on this device");
     std::copy(c.log_ms, c.log_ms + PBF_LOG_SORT_STAGES, ms_out);
     if (merge_passes_out) *merge_passes_out = c.log_passes;
+    return PBF_OK;
+}
+
+}  // extern "C"
+
+// ====================================================================== resident write path
+// The device planner (csrc/sstable_plan_kernels.hpp) and the two-phase job that turns resident
+// tables or a put log into resident tables: run and plan in `begin`, encode / filters / bounds /
+// validation in `finish`, straight into the allocations the new tables own.
+namespace {
+
+struct PlanWork {
+    DevBuf nxt, exh, segs, res;
+    void release() {
+        for (DevBuf* d : {&nxt, &exh, &segs, &res}) d->release();
+    }
+};
+
+// The plan of n > 0 records on s into the caller's device arrays of `cap` entries each; *r = the
+// counts.  Two waits: after k_plan_next (a record over block_size: refused, nothing further is
+// launched) and after the walk (the counts; the expansion only runs on a plan that fits).
+int plan_device_run(hipStream_t s, PlanWork& w, const uint64_t* ko, const uint64_t* vo, uint64_t n, uint64_t block_size,
+                    uint64_t max_sstable_size, uint64_t* bf, uint64_t* bo, uint64_t* tb, uint64_t cap, PlanResult* r) {
+    if (block_size == 0 || block_size > kMaxBlockData) return fail(PBF_ERR_INVALID, "block_size must be in (0, 65536]");
+    if (n == 0) return fail(PBF_ERR_INVALID, "an SSTable needs at least one record");
+    if (n >= 0xFFFFFFFFull) return fail(PBF_ERR_INVALID, "a planned run holds fewer than 2^32 - 1 records");
+    const uint64_t nchunks = (n + kPlanChunk - 1) / kPlanChunk;
+    HIP_TRY(w.nxt.ensure(n * 4));
+    HIP_TRY(w.exh.ensure(n * 8));
+    HIP_TRY(w.segs.ensure(nchunks * sizeof(PlanSeg)));
+    HIP_TRY(w.res.ensure(sizeof(PlanResult)));
+    auto* nxt = static_cast<uint32_t*>(w.nxt.p);
+    auto* exh = static_cast<uint64_t*>(w.exh.p);
+    auto* segs = static_cast<PlanSeg*>(w.segs.p);
+    auto* res = static_cast<PlanResult*>(w.res.p);
+    HIP_TRY(hipMemsetAsync(res, 0, sizeof(PlanResult), s));
+    k_plan_next<<<grid_for(n, 256, 1u << 16), 256, 0, s>>>(ko, vo, n, block_size, nxt, res);
+    CHECK_LAUNCH();
+    HIP_TRY(hipMemcpyAsync(r, res, sizeof(PlanResult), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (r->oversize) return fail(PBF_ERR_INVALID, "a record is larger than block_size");
+    HIP_TRY(hipMemsetAsync(segs, 0, nchunks * sizeof(PlanSeg), s));
+    k_plan_chunks<<<uint32_t(nchunks), kPlanThreads, 0, s>>>(nxt, n, exh);
+    CHECK_LAUNCH();
+    k_plan_walk<<<1, 64, 0, s>>>(ko, vo, n, max_sstable_size, nxt, exh, bf, bo, tb, cap, segs, res);
+    CHECK_LAUNCH();
+    HIP_TRY(hipMemcpyAsync(r, res, sizeof(PlanResult), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (r->overflow)
+        return fail(PBF_ERR_INVALID, "the plan does not fit cap_entries = " + std::to_string(cap) + " (n + 1 always does)");
+    k_plan_expand<<<uint32_t(nchunks), 256, 0, s>>>(ko, vo, n, nxt, segs, bf, bo);
+    CHECK_LAUNCH();
+    return PBF_OK;
+}
+
+constexpr int kJobStages = 5;  // run, plan, encode (with the bounds), filters, validate
+
+}  // namespace
+
+struct pbf_job {
+    int device = 0;
+    bool flush = false;
+    bool concat = false;        // PBF_MERGE_CONCAT: the run is in list order, as the reference writes it
+    DevBuf keys, vals, ko, vo;  // the run
+    uint64_t n = 0, kb = 0, vb = 0;
+    DevBuf bf, bo, tb;          // the plan
+    PlanWork work;
+    DevBuf bsz, boff, bnd_offs, bnd, err, rep;
+    std::vector<uint64_t> h_bf, h_bo, h_tb;
+    std::vector<uint32_t> h_bsz;  // bytes of every block's first and last key
+    uint64_t nblocks = 0, ntables = 0, written = 0;
+    hipEvent_t ev[kJobStages + 2] = {};
+    float ms[kJobStages] = {};
+};
+
+namespace {
+
+std::mutex g_job_mu;
+std::set<pbf_job_t*> g_jobs;
+std::mutex g_job_ms_mu;
+std::map<int, std::vector<float>> g_job_ms;  // the stage times of the last finished job per device
+
+// Frees a job: every library stream is waited for first (filter builds read the run).
+void job_free(pbf_job_t* j) {
+    (void)hipSetDevice(j->device);
+    (void)sync_library_streams();
+    for (DevBuf* d : {&j->keys, &j->vals, &j->ko, &j->vo, &j->bf, &j->bo, &j->tb, &j->bsz, &j->boff, &j->bnd_offs, &j->bnd,
+                      &j->err, &j->rep})
+        d->release();
+    j->work.release();
+    for (hipEvent_t e : j->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete j;
+}
+
+bool job_take(pbf_job_t* j) {
+    std::lock_guard<std::mutex> lock(g_job_mu);
+    return j && g_jobs.erase(j) == 1;
+}
+
+// The buffers of the run, once its totals are known (RunOut::alloc).
+auto job_run_alloc(pbf_job_t* j) {
+    return [j](uint64_t n, uint64_t kb, uint64_t vb, RunOut& o) -> int {
+        HIP_TRY(j->keys.ensure(kb + 32));
+        HIP_TRY(j->vals.ensure(vb + 32));
+        HIP_TRY(j->ko.ensure((n + 1) * 8));
+        HIP_TRY(j->vo.ensure((n + 1) * 8));
+        o.keys = static_cast<uint8_t*>(j->keys.p);
+        o.keys_cap = kb;
+        o.values = static_cast<uint8_t*>(j->vals.p);
+        o.values_cap = vb;
+        o.key_offsets = static_cast<uint64_t*>(j->ko.p);
+        o.value_offsets = static_cast<uint64_t*>(j->vo.p);
+        o.offsets_cap = n + 1;
+        return PBF_OK;
+    };
+}
+
+// After the run: the plan, its host copy and the sizes of the blocks' bound keys.
+int job_plan(pbf_job_t* j, hipStream_t s, uint64_t block_size, uint64_t max_sstable_size) {
+    HIP_TRY(hipEventRecord(j->ev[1], s));
+    j->h_bf.assign(1, 0);
+    j->h_bo.assign(1, 0);
+    j->h_tb.assign(1, 0);
+    if (j->n == 0) {  // (a compaction of nothing: no output)
+        HIP_TRY(hipEventRecord(j->ev[2], s));
+        return PBF_OK;
+    }
+    const uint64_t cap = j->n + 1;
+    HIP_TRY(j->bf.ensure(cap * 8));
+    HIP_TRY(j->bo.ensure(cap * 8));
+    HIP_TRY(j->tb.ensure(cap * 8));
+    auto* ko = static_cast<const uint64_t*>(j->ko.p);
+    auto* bf = static_cast<uint64_t*>(j->bf.p);
+    PlanResult r{};
+    int rc = plan_device_run(s, j->work, ko, static_cast<const uint64_t*>(j->vo.p), j->n, block_size, max_sstable_size, bf,
+                             static_cast<uint64_t*>(j->bo.p), static_cast<uint64_t*>(j->tb.p), cap, &r);
+    if (rc) return rc;
+    j->nblocks = r.nblocks;
+    j->ntables = r.ntables;
+    j->written = r.written;
+    HIP_TRY(hipEventRecord(j->ev[2], s));
+    j->h_bf.resize(j->nblocks + 1);
+    j->h_bo.resize(j->nblocks + 1);
+    j->h_tb.resize(j->ntables + 1);
+    j->h_bsz.resize(2 * j->nblocks);
+    HIP_TRY(hipMemcpyAsync(j->h_bf.data(), bf, (j->nblocks + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(j->h_bo.data(), j->bo.p, (j->nblocks + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(j->h_tb.data(), j->tb.p, (j->ntables + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (j->nblocks) {
+        HIP_TRY(j->bsz.ensure(2 * j->nblocks * 4));
+        k_plan_bound_sizes<<<grid_for(j->nblocks, 256, 1u << 24), 256, 0, s>>>(ko, bf, j->nblocks,
+                                                                             static_cast<uint32_t*>(j->bsz.p));
+        CHECK_LAUNCH();
+        HIP_TRY(hipMemcpyAsync(j->h_bsz.data(), j->bsz.p, 2 * j->nblocks * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    j->work.release();
+    return PBF_OK;
+}
+
+int job_new(int device, bool flush, pbf_job_t** out) {
+    HIP_TRY(hipSetDevice(device));
+    pbf_job_t* j = new pbf_job();
+    j->device = device;
+    j->flush = flush;
+    for (hipEvent_t& e : j->ev) {
+        const hipError_t err = hipEventCreate(&e);
+        if (err != hipSuccess) {
+            job_free(j);
+            return fail(PBF_ERR_HIP, std::string("hipEventCreate: ") + hipGetErrorString(err));
+        }
+    }
+    *out = j;
+    return PBF_OK;
+}
+
+int job_publish(pbf_job_t* j, int rc, pbf_job_t** out) {
+    if (rc) {
+        const std::string msg = g_last_error;
+        job_free(j);
+        return fail(rc, msg);
+    }
+    std::lock_guard<std::mutex> lock(g_job_mu);
+    g_jobs.insert(j);
+    *out = j;
+    return PBF_OK;
+}
+
+int job_stream(int device, hipStream_t* s) {
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    int rc = sst_ctx_stream(c, device);
+    *s = c.stream;
+    return rc;
+}
+
+int job_finish_run(pbf_job_t* j, pbf_filter_t* const* filters, uint32_t* block_off_out, uint8_t* bounds_out,
+                   uint64_t* bounds_offsets_out, pbf_sstable_t** tables_out, std::vector<pbf_sstable_t*>& made) {
+    const uint32_t nt = uint32_t(j->ntables);
+    if (nt == 0) return PBF_OK;
+    if (!filters || !block_off_out || !bounds_offsets_out || !tables_out) return fail(PBF_ERR_INVALID, "null pointer");
+    for (uint32_t t = 0; t < nt; ++t) {
+        if (!filters[t]) return fail(PBF_ERR_INVALID, "null filter in the set");
+        if (filters[t]->device != j->device) return fail(PBF_ERR_INVALID, "the outputs' filters must be on the job's device");
+        for (uint32_t u = 0; u < t; ++u)
+            if (filters[u] == filters[t]) return fail(PBF_ERR_INVALID, "a filter appears twice");
+        const uint64_t dl = j->h_bo[j->h_tb[t + 1]] - j->h_bo[j->h_tb[t]];
+        if (dl == 0 || dl > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "data section over 2 GiB (the file's offsets are i32)");
+    }
+    std::vector<pbf_filter_t*> order(filters, filters + nt);
+    std::sort(order.begin(), order.end());
+    std::vector<std::unique_lock<std::shared_mutex>> flocks;
+    flocks.reserve(nt);
+    for (pbf_filter_t* p : order) flocks.emplace_back(p->mu);
+    HIP_TRY(hipSetDevice(j->device));
+    HIP_TRY(allow_lds(k_encode_blocks, kEncodeLds));
+    SstCtx& c = sst_ctx(j->device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    int rc = sst_ctx_stream(c, j->device);
+    if (rc) return rc;
+    hipStream_t s = c.stream;
+    const uint64_t nb = j->nblocks;
+    // the new tables' allocations, the block offsets inside each section, the bound offsets
+    std::vector<uint32_t> boff;
+    boff.reserve(nb + nt);
+    std::vector<uint64_t> bnd_offs(2 * nb + 1, 0);
+    for (uint64_t i = 0; i < 2 * nb; ++i) bnd_offs[i + 1] = bnd_offs[i] + j->h_bsz[i];
+    for (uint32_t t = 0; t < nt; ++t) {
+        const uint64_t b0 = j->h_tb[t], b1 = j->h_tb[t + 1], o0 = j->h_bo[b0];
+        for (uint64_t b = b0; b <= b1; ++b) boff.push_back(uint32_t(j->h_bo[b] - o0));
+        pbf_sstable_t* tb = new pbf_sstable();
+        made.push_back(tb);
+        tb->device = j->device;
+        tb->data_len = j->h_bo[b1] - o0;
+        tb->nblocks = uint32_t(b1 - b0);
+        HIP_TRY(tb->data.ensure(tb->data_len + 16));
+        HIP_TRY(tb->index.ensure(size_t(tb->nblocks) * sizeof(SstBlock)));
+        HIP_TRY(tb->prefix.ensure(size_t(tb->nblocks) * 8));
+    }
+    HIP_TRY(j->boff.ensure(boff.size() * 4));
+    HIP_TRY(j->bnd_offs.ensure(bnd_offs.size() * 8));
+    HIP_TRY(j->bnd.ensure(bnd_offs.back() + 16));
+    HIP_TRY(j->err.ensure(4));
+    HIP_TRY(j->rep.ensure(sizeof(SstReport) * nt));
+    auto* dk = static_cast<const uint8_t*>(j->keys.p);
+    auto* dko = static_cast<const uint64_t*>(j->ko.p);
+    auto* dbf = static_cast<const uint64_t*>(j->bf.p);
+    auto* dbo = static_cast<const uint64_t*>(j->bo.p);
+    HIP_TRY(hipEventRecord(j->ev[3], s));
+    HIP_TRY(hipMemsetAsync(j->err.p, 0, 4, s));
+    for (uint32_t t = 0; t < nt; ++t) {
+        // block_out runs end to end over the outputs: section t starts at its first block's offset
+        const uint64_t b0 = j->h_tb[t], o0 = j->h_bo[b0];
+        uint8_t* data = static_cast<uint8_t*>(made[t]->data.p);
+        k_encode_blocks<<<made[t]->nblocks, 512, kEncodeLds, s>>>(dk, dko, static_cast<const uint8_t*>(j->vals.p),
+                                                                  static_cast<const uint64_t*>(j->vo.p), dbf + b0, dbo + b0,
+                                                                  data - o0, static_cast<unsigned int*>(j->err.p));
+        CHECK_LAUNCH();
+        HIP_TRY(hipMemsetAsync(data + made[t]->data_len, 0, 16, s));
+    }
+    HIP_TRY(hipMemcpyAsync(j->boff.p, boff.data(), boff.size() * 4, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(j->bnd_offs.p, bnd_offs.data(), bnd_offs.size() * 8, hipMemcpyHostToDevice, s));
+    k_plan_bounds_gather<<<grid_for(nb * 64, 256, 1u << 24), 256, 0, s>>>(dk, dko, dbf, nb,
+                                                                         static_cast<const uint64_t*>(j->bnd_offs.p),
+                                                                         static_cast<uint8_t*>(j->bnd.p));
+    CHECK_LAUNCH();
+    if (bnd_offs.back()) {
+        if (!bounds_out) return fail(PBF_ERR_INVALID, "null pointer");
+        HIP_TRY(hipMemcpyAsync(bounds_out, j->bnd.p, bnd_offs.back(), hipMemcpyDeviceToHost, s));
+    }
+    unsigned int err = 0;
+    HIP_TRY(hipMemcpyAsync(&err, j->err.p, 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipEventRecord(j->ev[4], s));
+    // every output's filter from its slice of the run's keys, on the filter's own stream
+    const Batch all = make_batch(dk, dko, 0, j->written);
+    for (uint32_t t = 0; t < nt; ++t) {
+        pbf_filter_t* ft = filters[t];
+        const uint64_t r0 = j->h_bf[j->h_tb[t]], r1 = j->h_bf[j->h_tb[t + 1]];
+        if (ft->k > 0) {  // SSTableBuilder.build's filter over the output's keys (sstable.py:274)
+            Lease lt(ft);
+            rc = lt.acquire();
+            if (!rc) rc = add_device(ft, slice(all, r0, r1 - r0));
+            if (rc) return rc;
+        }
+        ft->pending = true;
+        HIP_TRY(filter_event(ft));
+        HIP_TRY(hipEventRecord(ft->ev, ft->stream));
+        HIP_TRY(hipStreamWaitEvent(s, ft->ev, 0));
+    }
+    HIP_TRY(hipEventRecord(j->ev[5], s));
+    std::vector<const uint32_t*> offs(nt);
+    size_t at = 0;
+    for (uint32_t t = 0; t < nt; ++t) {
+        offs[t] = static_cast<const uint32_t*>(j->boff.p) + at;
+        at += made[t]->nblocks + 1;
+    }
+    std::vector<SstReport> reps(nt);
+    if ((rc = sst_index_tables(s, made.data(), offs.data(), nt, static_cast<SstReport*>(j->rep.p), reps.data()))) return rc;
+    HIP_TRY(hipEventRecord(j->ev[6], s));
+    HIP_TRY(hipEventSynchronize(j->ev[6]));
+    for (uint32_t t = 0; t < nt; ++t)
+        if (filters[t]->pending) WAIT(filters[t]);
+    if (err) return fail(PBF_ERR_INVALID, std::to_string(err) + " block(s) exceed 65536 data bytes; not written");
+    for (uint32_t t = 0; t < nt; ++t) {
+        // a concatenation of tables that are out of key order gives outputs whose keys do not
+        // ascend, as in the reference (_compact writes what ConcatenatingIterator yields): framing
+        // and sizes hold, so no lookup leaves the section, but only its records() are meaningful
+        SstReport rr = reps[t];
+        if (j->concat && !rr.bad_blocks && !rr.bad_records && !(rr.rules & ~kSstRuleOrder)) {
+            rr.rules = 0;
+            rr.order_violations = 0;
+        }
+        if (sst_report_bad(rr)) return sst_refuse(rr);
+        made[t]->nrecords = reps[t].records;
+        if (made[t]->nrecords != j->h_bf[j->h_tb[t + 1]] - j->h_bf[j->h_tb[t]])
+            return fail(PBF_ERR_INVALID, "an encoded output does not hold its planned records");
+    }
+    std::copy(boff.begin(), boff.end(), block_off_out);
+    std::copy(bnd_offs.begin(), bnd_offs.end(), bounds_offsets_out);
+    std::vector<float> ms(kJobStages, 0.f);
+    for (int i = 0; i < kJobStages; ++i) {
+        const int a = i < 2 ? i : i + 1;  // (ev[2] closes `begin`, ev[3] opens `finish`)
+        HIP_TRY(hipEventElapsedTime(&ms[i], j->ev[a], j->ev[a + 1]));
+    }
+    {
+        std::lock_guard<std::mutex> l(g_job_ms_mu);
+        g_job_ms[j->device] = ms;
+    }
+    return PBF_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbf_plan_device(int device, void* stream, const uint64_t* key_offsets_dev, const uint64_t* value_offsets_dev,
+                    uint64_t n, uint64_t block_size, uint64_t max_sstable_size, uint64_t* block_first_dev,
+                    uint64_t* block_out_dev, uint64_t* table_blocks_dev, uint64_t cap_entries, uint64_t* nblocks,
+                    uint64_t* ntables, uint64_t* written) {
+    if (!key_offsets_dev || !value_offsets_dev || !block_first_dev || !block_out_dev || !table_blocks_dev || !nblocks ||
+        !ntables || !written)
+        return fail(PBF_ERR_INVALID, "null pointer");
+    HIP_TRY(hipSetDevice(device));
+    PlanWork w;
+    PlanResult r{};
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    int rc = plan_device_run(s, w, key_offsets_dev, value_offsets_dev, n, block_size, max_sstable_size, block_first_dev,
+                             block_out_dev, table_blocks_dev, cap_entries, &r);
+    const std::string msg = g_last_error;
+    const hipError_t e = hipStreamSynchronize(s);
+    w.release();
+    if (rc) return fail(rc, msg);
+    HIP_TRY(e);
+    *nblocks = r.nblocks;
+    *ntables = r.ntables;
+    *written = r.written;
+    return PBF_OK;
+}
+
+int pbf_compact_begin(pbf_sstable_t* const* tables, uint32_t ntables, int mode, uint64_t block_size,
+                      uint64_t max_sstable_size, pbf_job_t** job, uint64_t* ntables_out, uint64_t* written) {
+    if (!job || !ntables_out || !written) return fail(PBF_ERR_INVALID, "null pointer");
+    *job = nullptr;
+    if (block_size == 0 || block_size > kMaxBlockData) return fail(PBF_ERR_INVALID, "block_size must be in (0, 65536]");
+    if (max_sstable_size == 0) return fail(PBF_ERR_INVALID, "max_sstable_size must be positive");
+    int rc = check_run_tables(tables, ntables, "merge");
+    if (rc) return rc;
+    int device = 0;
+    {
+        SstLocks probe;  // (the handles are judged before anything is allocated)
+        if ((rc = probe.take(tables, ntables))) return rc;
+        device = tables[0]->device;
+    }
+    pbf_job_t* j = nullptr;
+    if ((rc = job_new(device, false, &j))) return rc;
+    j->concat = mode == PBF_MERGE_CONCAT;
+    hipStream_t s = nullptr;
+    rc = job_stream(device, &s);
+    if (!rc && hipEventRecord(j->ev[0], s) != hipSuccess) rc = fail(PBF_ERR_HIP, "hipEventRecord");
+    if (!rc)
+        rc = sst_merge_run(tables, ntables, mode,
+                           RunOut{nullptr, 0, nullptr, nullptr, 0, nullptr, 0, &j->n, &j->kb, &j->vb, 1, s, job_run_alloc(j)},
+                           true);
+    if (!rc) rc = job_plan(j, s, block_size, max_sstable_size);
+    if ((rc = job_publish(j, rc, job))) return rc;
+    *ntables_out = j->ntables;
+    *written = j->written;
+    return PBF_OK;
+}
+
+int pbf_flush_begin(int device, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
+                    const uint64_t* value_offsets, uint64_t n, uint64_t block_size, pbf_job_t** job) {
+    if (!job) return fail(PBF_ERR_INVALID, "null pointer");
+    *job = nullptr;
+    if (block_size == 0 || block_size > kMaxBlockData) return fail(PBF_ERR_INVALID, "block_size must be in (0, 65536]");
+    if (n == 0) return fail(PBF_ERR_INVALID, "an SSTable needs at least one record");
+    pbf_job_t* j = nullptr;
+    int rc = job_new(device, true, &j);
+    if (rc) return rc;
+    hipStream_t s = nullptr;
+    rc = job_stream(device, &s);
+    if (!rc && hipEventRecord(j->ev[0], s) != hipSuccess) rc = fail(PBF_ERR_HIP, "hipEventRecord");
+    if (!rc)
+        rc = log_sort_run(device, keys, key_offsets, values, value_offsets, n,
+                          RunOut{nullptr, 0, nullptr, nullptr, 0, nullptr, 0, &j->n, &j->kb, &j->vb, 1, s, job_run_alloc(j)},
+                          nullptr);
+    if (!rc) rc = job_plan(j, s, block_size, 0);
+    return job_publish(j, rc, job);
+}
+
+int pbf_job_table_info(pbf_job_t* job, uint32_t t, uint64_t* nrecords, uint64_t* nblocks, uint64_t* data_len,
+                       uint64_t* bound_key_bytes) {
+    std::lock_guard<std::mutex> lock(g_job_mu);
+    if (!job || !g_jobs.count(job)) return fail(PBF_ERR_INVALID, "null, finished or unknown job handle");
+    if (t >= job->ntables) return fail(PBF_ERR_INVALID, "the job has " + std::to_string(job->ntables) + " output(s)");
+    const uint64_t b0 = job->h_tb[t], b1 = job->h_tb[t + 1];
+    if (nrecords) *nrecords = job->h_bf[b1] - job->h_bf[b0];
+    if (nblocks) *nblocks = b1 - b0;
+    if (data_len) *data_len = job->h_bo[b1] - job->h_bo[b0];
+    if (bound_key_bytes) {
+        uint64_t sum = 0;
+        for (uint64_t i = 2 * b0; i < 2 * b1; ++i) sum += job->h_bsz[i];
+        *bound_key_bytes = sum;
+    }
+    return PBF_OK;
+}
+
+int pbf_job_finish(pbf_job_t* job, pbf_filter_t* const* filters, uint32_t* block_off_out, uint8_t* bounds_out,
+                   uint64_t* bounds_offsets_out, pbf_sstable_t** tables_out) {
+    if (!job_take(job)) return fail(PBF_ERR_INVALID, "null, finished or unknown job handle");
+    std::vector<pbf_sstable_t*> made;
+    int rc = job_finish_run(job, filters, block_off_out, bounds_out, bounds_offsets_out, tables_out, made);
+    const std::string msg = g_last_error;
+    if (rc) {  // no table is registered and nothing stays allocated
+        (void)hipSetDevice(job->device);
+        (void)sync_library_streams();
+        for (pbf_sstable_t* t : made) {
+            sst_free(t);
+            delete t;
+        }
+    } else {
+        for (size_t t = 0; t < made.size(); ++t) {
+            sst_register(made[t]);
+            tables_out[t] = made[t];
+        }
+    }
+    job_free(job);
+    return rc ? fail(rc, msg) : PBF_OK;
+}
+
+int pbf_job_abort(pbf_job_t* job) {
+    if (!job) return PBF_OK;
+    if (!job_take(job)) return fail(PBF_ERR_INVALID, "finished or unknown job handle");
+    job_free(job);
+    return PBF_OK;
+}
+
+int pbf_job_stage_ms(int device, float* ms_out) {
+    if (!ms_out) return fail(PBF_ERR_INVALID, "null pointer");
+    std::lock_guard<std::mutex> l(g_job_ms_mu);
+    auto it = g_job_ms.find(device);
+    if (it == g_job_ms.end()) return fail(PBF_ERR_INVALID, "no finished job on this device");
+    std::copy(it->second.begin(), it->second.end(), ms_out);
+    return PBF_OK;
+}
+
+int pbf_sst_read_data(pbf_sstable_t* t, uint8_t* out_host, uint64_t len) {
+    SstLocks locks;
+    int rc = locks.take(&t, 1);
+    if (rc) return rc;
+    if (!out_host || len != t->data_len) return fail(PBF_ERR_INVALID, "out must hold the table's data_len bytes");
+    HIP_TRY(hipSetDevice(t->device));
+    hipStream_t s = nullptr;
+    if ((rc = job_stream(t->device, &s))) return rc;
+    HostPins pins;
+    pins.pin(out_host, len);
+    HIP_TRY(hipMemcpyAsync(out_host, t->data.p, len, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return PBF_OK;
 }
 

@@ -13,7 +13,8 @@ merge passes by rank — a mark of the last put of every key, and the compaction
 packed copy.  ``flush_log`` is ``sort_log`` followed by ``sstable_data.build_sstable``: the bytes
 of the ``.sst`` file ``_do_flush`` writes.  ``flush_wal`` starts from a WAL file or its bytes
 (``PackedRecords.from_wal``): ``create_from_wal`` plus ``_do_flush``, without the state update and
-the manifest event, which stay with the caller.
+the manifest event, which stay with the caller.  ``flush_log_resident`` / ``flush_wal_resident`` keep
+the sorted run on the device and return the flushed table as an open ``DeviceSSTable``.
 
 Keys order as unsigned bytes, which is the reference's ``str`` order for ASCII keys; a non-ASCII
 key is refused, as ``DeviceSSTable`` refuses a table that stores one (the reference writes
@@ -29,7 +30,7 @@ import numpy as np
 
 from . import _native
 from .keys import PackedKeys, PackedRecords
-from .sstable_data import BLOCK_SIZE, build_sstable, key_offsets
+from .sstable_data import BLOCK_SIZE, _check_block_size, build_sstable, key_offsets
 
 _vp = ctypes.c_void_p
 SORT_TILE = 2048   # kMtTile: entries one workgroup sorts in LDS
@@ -58,6 +59,14 @@ def _ptr(a: np.ndarray):
     return _vp(a.ctypes.data) if a.size else None
 
 
+def _log_arrays(log: PackedRecords):
+    """(keys, key offsets, values, value offsets) of a log as ``pbf_log_sort`` reads them."""
+    return (np.ascontiguousarray(log.keys.data, dtype=np.uint8),
+            np.ascontiguousarray(key_offsets(log.keys), dtype=np.uint64),
+            np.ascontiguousarray(log.values, dtype=np.uint8).reshape(-1),
+            np.ascontiguousarray(log.value_offsets, dtype=np.uint64))
+
+
 def sort_log(puts, device=None, with_index: bool = False):
     """``MemTableIterator``'s run of a put log: every distinct key ascending, each with the value
     of its last put, as a ``PackedRecords`` (``ascii=True``).  `puts` is a ``PackedRecords`` in put
@@ -68,10 +77,7 @@ def sort_log(puts, device=None, with_index: bool = False):
     log = _as_log(puts)
     dev = _default_device if device is None else int(device)
     n = log.n
-    ko = np.ascontiguousarray(key_offsets(log.keys), dtype=np.uint64)
-    vo = np.ascontiguousarray(log.value_offsets, dtype=np.uint64)
-    kin = np.ascontiguousarray(log.keys.data, dtype=np.uint8)
-    vin = np.ascontiguousarray(log.values, dtype=np.uint8).reshape(-1)
+    kin, ko, vin, vo = _log_arrays(log)
     kbytes, vbytes = (int(ko[-1]), int(vo[-1])) if n else (0, 0)
     keys, values = np.empty(kbytes, dtype=np.uint8), np.empty(vbytes, dtype=np.uint8)
     oko, ovo = np.empty(n + 1, dtype=np.uint64), np.empty(n + 1, dtype=np.uint64)
@@ -97,7 +103,39 @@ def flush_log(puts, block_size: int = BLOCK_SIZE, fp_rate: float = 0.001, device
 def flush_wal(wal, block_size: int = BLOCK_SIZE, fp_rate: float = 0.001, device=None):
     """``MemTable.create_from_wal`` plus ``_do_flush`` up to the file: `wal` is the path of a WAL
     file or its bytes (``PackedRecords.from_wal``), then ``flush_log``."""
+    return flush_log(_wal_log(wal), block_size, fp_rate, device)
+
+
+def _wal_log(wal) -> PackedRecords:
     if isinstance(wal, (str, os.PathLike)):
         with open(wal, "rb") as f:
             wal = f.read()
-    return flush_log(PackedRecords.from_wal(wal), block_size, fp_rate, device)
+    return PackedRecords.from_wal(wal)
+
+
+def flush_log_resident(puts, block_size: int = BLOCK_SIZE, fp_rate: float = 0.001, device=None):
+    """``flush_log`` without the way back: the log goes up once, the sorted run stays on the device,
+    where it is planned, encoded, filtered and opened.  Returns the ``DeviceSSTable``; its
+    ``to_bytes()`` is the file ``flush_log`` returns.  An empty log raises as ``build_sstable``
+    does on an empty run, a non-ASCII key as ``flush_log`` does."""
+    from .bloom_filter import _default_device
+    from .resident_write import finish_job
+
+    log = _as_log(puts)
+    _check_block_size(block_size)
+    if log.n == 0:
+        raise ValueError("an SSTable needs at least one record (the reference fails in MetaBlock.to_bytes)")
+    dev = _default_device if device is None else int(device)
+    kin, ko, vin, vo = _log_arrays(log)
+    job = _vp()
+    rc = _native.lib().pbf_flush_begin(dev, _ptr(kin), _vp(ko.ctypes.data), _ptr(vin), _vp(vo.ctypes.data), log.n,
+                                       block_size, ctypes.byref(job))
+    if rc == _native.PBF_ERR_INVALID and "larger than block_size" in _native.lib().pbf_last_error().decode():
+        raise ValueError("a record is larger than block_size (the reference would drop it, blocks.py:84-85)")
+    _native.check(rc, "pbf_flush_begin")
+    return finish_job(job, 1, fp_rate, dev)[0]
+
+
+def flush_wal_resident(wal, block_size: int = BLOCK_SIZE, fp_rate: float = 0.001, device=None):
+    """``flush_wal`` without the way back: `wal` as there, then ``flush_log_resident``."""
+    return flush_log_resident(_wal_log(wal), block_size, fp_rate, device)

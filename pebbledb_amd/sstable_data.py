@@ -99,6 +99,24 @@ def plan_blocks_native(ko: np.ndarray, vo: np.ndarray, block_size: int = BLOCK_S
     return bf[:nb.value + 1].copy(), bo[:nb.value + 1].copy()
 
 
+def filter_sizing(n: int, fp_rate: float) -> tuple[int, int]:
+    """(nb_bytes, k) of an output's filter over its n keys: build_from_keys_and_fp_rate's sizing
+    (bloom_filter.py:109-114, same expression order, Python's round); a k that to_bytes could not
+    store raises the struct.error SSTableEncoding.to_bytes would."""
+    from math import ceil, log
+
+    m = (-n * log(fp_rate)) / (log(2) ** 2)
+    nb_bytes, k = ceil(m / 8), round((m / n) * log(2))
+    if not 0 <= k <= 255:
+        raise struct.error("ubyte format requires 0 <= number <= 255")  # SSTableEncoding -> to_bytes
+    return nb_bytes, k
+
+
+def _check_block_size(block_size: int) -> None:
+    if not 0 < block_size <= 65_536:
+        raise ValueError("block_size must be in (0, 65536]: DataBlock offsets are u16 (blocks.py:34)")
+
+
 def _check_max_sstable_size(max_sstable_size: int) -> None:
     """A split size of 0 or less is refused.  (The reference checks the position after every
     add, lsm_storage.py:241, so there it would build one SSTable per record; the planners here
@@ -234,8 +252,6 @@ def build_sstable(keys, values=None, block_size: int = BLOCK_SIZE, fp_rate: floa
     to the GPU once, the data blocks and the filter (build_from_keys_and_fp_rate's sizing,
     bloom_filter.py:109-114, fp 0.001 as sstable.py:274) are both built from that copy, and the
     data section and the bitmap are copied straight into their slices of the file buffer."""
-    from math import ceil, log
-
     from .bloom_filter import BloomFilter, _default_device
     from .sstable_bloom import TRAILER, sstable_size
 
@@ -255,10 +271,7 @@ def build_sstable(keys, values=None, block_size: int = BLOCK_SIZE, fp_rate: floa
     bf_first, bo = plan_blocks_native(ko, vo, block_size)
     meta, metas = meta_blocks(keys if isinstance(keys, list) else pk, bf_first, bo)
     n = pk.n
-    m = (-n * log(fp_rate)) / (log(2) ** 2)  # bloom_filter.py:109-114, same expression order
-    nb_bytes, k = ceil(m / 8), round((m / n) * log(2))
-    if not 0 <= k <= 255:
-        raise struct.error("ubyte format requires 0 <= number <= 255")  # SSTableEncoding -> to_bytes
+    nb_bytes, k = filter_sizing(n, fp_rate)
     bloom = BloomFilter(nb_bytes, k, device=dev)
     data_len = int(bo[-1])
     if data_len + len(meta) > 0x7FFFFFFF:
@@ -291,8 +304,6 @@ def build_sstables(keys, values=None, max_sstable_size: int = 262_144_000, block
     outputs = [(file bytes as a uint8 numpy array, meta blocks, filter), ...] in the order
     _compact returns them, written = records covered (the reference leaves out records still in
     its last builder's first open block)."""
-    from math import ceil, log
-
     from .bloom_filter import BloomFilter, _default_device
     from .sstable_bloom import TRAILER, sstable_size
 
@@ -318,10 +329,7 @@ def build_sstables(keys, values=None, max_sstable_size: int = 262_144_000, block
     for t in range(nt):
         b0, b1 = int(tb[t]), int(tb[t + 1])
         n = int(bf[b1] - bf[b0])
-        m = (-n * log(fp_rate)) / (log(2) ** 2)  # bloom_filter.py:109-114, same expression order
-        nb_bytes, k = ceil(m / 8), round((m / n) * log(2))
-        if not 0 <= k <= 255:
-            raise struct.error("ubyte format requires 0 <= number <= 255")
+        nb_bytes, k = filter_sizing(n, fp_rate)
         base = int(bo[b0])
         meta, metas = meta_blocks(key_src, bf[b0:b1 + 1], bo[b0:b1 + 1] - np.uint64(base))
         data_len = int(bo[b1]) - base

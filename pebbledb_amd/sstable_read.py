@@ -180,6 +180,50 @@ class DeviceSSTable:
             raise
         return self
 
+    @classmethod
+    def _from_handle(cls, handle, device: int, metas, bloom: BloomFilter, nblocks: int, nrecords: int,
+                     data_len: int) -> "DeviceSSTable":
+        """A table the device built in place (``resident_write``): the attributes ``from_bytes``
+        sets, from what the job reported."""
+        self = object.__new__(cls)
+        self._h = handle
+        self.device = device
+        self.meta_blocks = metas
+        self.meta_block_offset = data_len
+        self.first_key, self.last_key = metas[0][0], metas[-1][1]
+        self.bloom_filter = bloom
+        self.nblocks, self.nrecords, self.data_len = nblocks, nrecords, data_len
+        return self
+
+    def to_bytes(self) -> np.ndarray:
+        """The table's ``.sst`` file (SSTableEncoding.to_bytes, sstable.py:80-86) as a uint8 array:
+        the data section copied from the device (``pbf_sst_read_data``), the meta blocks
+        (MetaBlock.to_bytes, blocks.py:126-133), the bloom section and the trailer -- what
+        ``build_sstable(s)`` returns for the same records, and for a table opened with
+        ``from_bytes`` the bytes it was opened from."""
+        from .sstable_bloom import TRAILER, sstable_size
+
+        if self._h is None:
+            raise ValueError("the SSTable is closed")
+        meta = b"".join(struct.pack("H", len(first)) + first.encode("utf-8") + struct.pack("H", len(last)) +
+                        last.encode("utf-8") + struct.pack("i", off) for first, last, off in self.meta_blocks)
+        bloom = self.bloom_filter.to_bytes()  # bitmap and the k byte
+        data_len = self.data_len
+        if data_len + len(meta) > 0x7FFFFFFF:
+            raise struct.error("'i' format requires -2147483648 <= number <= 2147483647")
+        out = np.empty(sstable_size(data_len, len(meta), len(bloom) - 1), dtype=np.uint8)
+        _native.check(_native.lib().pbf_sst_read_data(self._h, _vp(out.ctypes.data), data_len), "pbf_sst_read_data")
+        bloom_off = data_len + len(meta)
+        out[data_len:bloom_off] = np.frombuffer(meta, dtype=np.uint8)
+        out[bloom_off:bloom_off + len(bloom)] = np.frombuffer(bloom, dtype=np.uint8)
+        out[len(out) - TRAILER:] = np.frombuffer(struct.pack("ii", data_len, bloom_off), dtype=np.uint8)
+        return out
+
+    def write(self, path) -> None:
+        """Writes ``to_bytes()`` to `path`."""
+        with open(path, "wb") as f:
+            f.write(self.to_bytes().data)
+
     def _check_meta_keys(self, data: np.ndarray) -> None:
         """Every meta block's first / last key is the key of the block's first / last record in
         the validated index (the lookup trusts the index; LsmStorage.get's range check trusts

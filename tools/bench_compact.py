@@ -19,6 +19,11 @@ Prints one JSON line:
 * compact_l0_ms — the whole ``compact_l0`` (merge to host memory, plan, ``pbf_build_sstables``,
   files in host memory), a host clock around the synchronous call (it works on the library's own
   streams, which a caller's events do not bracket);
+* compact_l0_resident_ms — ``compact_l0_resident`` on the same tables in the same process, its
+  steps alternating with compact_l0's (host clock; the outputs are closed outside the timed part);
+  resident_stage_ms — the device time of its last job by stage (HIP events: run, plan, encode,
+  filters, validate); resident_to_bytes_ms — ``to_bytes()`` of every output of one step, the file
+  download a caller may ask for, timed apart; *_spread_ms — max - min of each path's steps;
 * host_path_s — the same run produced on the host from the same file bytes: the records of
   every table decoded in Python, ``heapq.merge`` keyed (key, table), duplicates dropped,
   ``PackedRecords.from_iter`` — once (it takes seconds, not milliseconds), and checked equal to
@@ -140,14 +145,30 @@ def main() -> None:
     n_out, kb, vb = (x.value for x in tot)
     merge_bytes = data_bytes + kb + vb + 2 * 8 * (n_out + 1)
 
-    # the whole compact_l0
-    compact_ms, outs = [], None
+    # the whole compact_l0, and compact_l0_resident on the same tables, step by step in turn
+    from pebbledb_amd.resident_write import last_stage_ms
+
+    compact_ms, resident_ms, to_bytes_ms, outs = [], [], [], None
     for step in range(a.warmup + a.steps):
         t0 = time.perf_counter()
         outs, written = compaction.compact_l0(tables)
         dt = (time.perf_counter() - t0) * 1e3
+        t0 = time.perf_counter()
+        res, res_written = compaction.compact_l0_resident(tables)
+        rdt = (time.perf_counter() - t0) * 1e3
+        assert res_written == written and len(res) == len(outs)
         if step >= a.warmup:
             compact_ms.append(dt)
+            resident_ms.append(rdt)
+        if step == a.warmup + a.steps - 1:
+            t0 = time.perf_counter()
+            got = [t.to_bytes() for t in res]
+            to_bytes_ms.append((time.perf_counter() - t0) * 1e3)
+            assert all(np.array_equal(g, f) for g, (f, _, _) in zip(got, outs))
+            del got
+        for t in res:
+            t.close()
+    stage_ms = last_stage_ms(tables[0].device)
     out_bytes = sum(len(f) for f, _, _ in outs)
 
     host_s = None
@@ -170,6 +191,12 @@ def main() -> None:
         "merge_pct_of_hbm_peak": round(100 * gbps / HBM_PEAK_GBPS, 2),
         "compact_l0_ms": round(float(np.median(compact_ms)), 2), "compact_l0_ms_all": [round(x, 2) for x in compact_ms],
         "compact_l0_outputs": len(outs), "compact_l0_file_bytes": out_bytes, "compact_l0_records_written": written,
+        "compact_l0_spread_ms": round(max(compact_ms) - min(compact_ms), 2),
+        "compact_l0_resident_ms": round(float(np.median(resident_ms)), 2),
+        "compact_l0_resident_ms_all": [round(x, 2) for x in resident_ms],
+        "compact_l0_resident_spread_ms": round(max(resident_ms) - min(resident_ms), 2),
+        "resident_stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
+        "resident_to_bytes_ms": round(to_bytes_ms[0], 2),
         "host_path_s": None if host_s is None else round(host_s, 2), "setup_s": round(t_build, 1),
     }
     print(json.dumps(out))

@@ -14,6 +14,11 @@ Prints one JSON line:
   the totals between them is inside), k_mt_copy, download of the run;
 * sort_log_ms — the whole synchronous ``sort_log`` call (host memory in, host memory out), a host
   clock; flush_log_ms — ``sort_log`` plus ``build_sstable``: the file in host memory;
+* flush_log_resident_ms — ``flush_log_resident`` on the same log in the same process, its steps
+  alternating with flush_log's (host clock; the table is closed outside the timed part);
+  resident_stage_ms — the device time of its last job by stage (HIP events: run, with the log's
+  upload; plan; encode; filters; validate); resident_to_bytes_ms — ``to_bytes()`` of the table,
+  the file download a caller may ask for, timed apart; *_spread_ms — max - min of a path's steps;
 * host_path_s — the same run produced on the host from the same puts as (str, bytes) pairs:
   Python ``dict`` (last put wins), ``sorted``, ``PackedRecords.from_iter`` — once, and checked
   equal to the device run; sort_log_speedup = host_path_s / sort_log_ms.
@@ -78,14 +83,27 @@ def main() -> None:
             stage_ms.append(list(ms))
     assert run.n == distinct
 
-    flush_ms, file_len = [], 0
+    from pebbledb_amd.resident_write import last_stage_ms
+
+    flush_ms, resident_ms, to_bytes_ms, file_len = [], [], 0.0, 0
     for step in range(a.warmup + a.steps):
         t0 = time.perf_counter()
         f, _, _ = memtable.flush_log(log)
         dt = (time.perf_counter() - t0) * 1e3
         file_len = len(f)
+        t0 = time.perf_counter()
+        table = memtable.flush_log_resident(log)
+        rdt = (time.perf_counter() - t0) * 1e3
         if step >= a.warmup:
             flush_ms.append(dt)
+            resident_ms.append(rdt)
+        if step == a.warmup + a.steps - 1:
+            t0 = time.perf_counter()
+            got = table.to_bytes()
+            to_bytes_ms = (time.perf_counter() - t0) * 1e3
+            assert np.array_equal(got, f)
+        table.close()
+    res_stage_ms = last_stage_ms(0)
 
     host_s = None
     if not a.skip_host:
@@ -111,6 +129,13 @@ def main() -> None:
         "sort_log_ms": round(med, 3), "sort_log_ms_all": [round(x, 3) for x in sort_ms],
         "sort_log_puts_per_s": round(n / (med * 1e-3)),
         "flush_log_ms": round(float(np.median(flush_ms)), 3), "flush_log_file_bytes": file_len,
+        "flush_log_ms_all": [round(x, 3) for x in flush_ms],
+        "flush_log_spread_ms": round(max(flush_ms) - min(flush_ms), 3),
+        "flush_log_resident_ms": round(float(np.median(resident_ms)), 3),
+        "flush_log_resident_ms_all": [round(x, 3) for x in resident_ms],
+        "flush_log_resident_spread_ms": round(max(resident_ms) - min(resident_ms), 3),
+        "resident_stage_ms": {k: round(v, 4) for k, v in res_stage_ms.items()},
+        "resident_to_bytes_ms": round(to_bytes_ms, 3),
         "host_path_s": None if host_s is None else round(host_s, 3),
         "sort_log_speedup": None if host_s is None else round(host_s / (med * 1e-3), 1),
         "setup_s": round(setup_s, 1),
