@@ -592,6 +592,85 @@ int pbf_job_stage_ms(int device, float* ms_out);
 /* Copies a resident table's data section (len = its data_len) to host memory, for the file. */
 int pbf_sst_read_data(pbf_sstable_t* t, uint8_t* out_host, uint64_t len);
 
+/* ---- Device memtable: MemTable (src/memtable.py) as one resident sorted run, searched and windowed
+ * on the device, in front of the tables in LsmStorage.get (src/lsm_storage.py:153-162: the active
+ * memtable, then the immutable ones, deque index 0 first) and LsmStorage.scan (:184-190).
+ * A memtable owns ONE run in device memory: its records strictly ascending and de-duplicated in
+ * pbf_sst_merge's output layout, plus the 8-byte prefix of every key (csrc/memtable_read_kernels.hpp).
+ * Readers hold the handle's lock shared, pbf_mt_apply and pbf_mt_destroy exclusively; asynchronous
+ * readers leave a per-stream event both wait for before a run is freed.  At most
+ * PBF_MT_MAX_PER_CALL memtables per call, memtables + tables <= 64, all on one device; a handle
+ * listed twice, a null or destroyed handle: PBF_ERR_INVALID. */
+#define PBF_MT_MAX_PER_CALL 16
+typedef struct pbf_memtable pbf_memtable_t;
+
+/* MemTable() (memtable.py:17-27): an empty memtable on `device`.  pbf_mt_destroy waits for every
+ * reader, then frees the run; a destroyed handle is refused by every later call. */
+int pbf_mt_create(int device, pbf_memtable_t** out);
+int pbf_mt_destroy(pbf_memtable_t* mt);
+
+/* MemTable.put x n (memtable.py:64-72; the tree replaces the data of a key it holds,
+ * red_black_tree.py:118-120): a put log in put order, in host memory, packed and checked as
+ * pbf_log_sort's input.  The log is sorted on the device by pbf_log_sort's chain and merged with the
+ * current run, the new batch winning every shared key, into a new run; the old one is freed once
+ * its readers are done.  n == 0 is a no-op; the first batch of an empty memtable is not merged.
+ * Synchronous. */
+int pbf_mt_apply(pbf_memtable_t* mt, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
+                 const uint64_t* value_offsets, uint64_t n);
+
+/* The run's records and its key and value bytes (any pointer may be NULL). */
+int pbf_mt_info(pbf_memtable_t* mt, uint64_t* nrecords, uint64_t* key_bytes, uint64_t* value_bytes);
+
+/* MemTableIterator's whole run (src/iterators.py:24-55) to host memory, pbf_log_sort's run of every
+ * put so far: both offsets arrays receive nrecords + 1 entries.  Capacities as in pbf_sst_merge: too
+ * small is PBF_ERR_INVALID with the size needed in the message, nothing written. */
+int pbf_mt_read(pbf_memtable_t* mt, uint8_t* keys_out, uint64_t keys_cap, uint64_t* key_offsets_out, uint8_t* values_out,
+                uint64_t values_cap, uint64_t* value_offsets_out, uint64_t offsets_cap);
+
+/* MemTable.get (memtable.py:74-79) for n keys (layouts as pbf_probe) over the memtables in list
+ * order, as LsmStorage.get reads them (lsm_storage.py:155-162): src_out[i] = the index of the
+ * first memtable that holds key i, or -1; val_off_out[i] = the value's offset in that memtable's
+ * value bytes; val_len_out[i] = its length, -1 if absent (0 is a stored empty value: the reference
+ * tests `is not None`).  miss_mask_out: ceil(n/8) bytes in the hit-mask layout, bit i set iff no
+ * memtable holds key i, pad bits zero: ANDed into the tables' candidate masks, a key a memtable
+ * answered is searched in no table.  on_device / stream as pbf_sst_get. */
+int pbf_mt_get(pbf_memtable_t* const* mts, uint32_t nmts, const uint8_t* keys, const uint64_t* offsets, uint32_t key_len,
+               uint64_t n, int on_device, void* stream, int32_t* src_out, uint64_t* val_off_out, int32_t* val_len_out,
+               uint8_t* miss_mask_out);
+
+/* pbf_sst_gather for a batch whose hits come partly from memtables and partly from tables
+ * (LsmStorage.get's return value, lsm_storage.py:155-179): where[i] >= 0 names tables[where[i]]
+ * (val_off into its data section), -2 - m names mts[m] (val_off into its value bytes), -1 nothing.
+ * Outputs, capacities, on_device and stream as pbf_sst_gather; ntables may be 0. */
+int pbf_mt_gather(pbf_memtable_t* const* mts, uint32_t nmts, pbf_sstable_t* const* tables, uint32_t ntables,
+                  const int32_t* where, const uint64_t* val_off, const int32_t* val_len, uint64_t n, uint8_t* out_bytes,
+                  uint64_t out_cap, uint64_t* out_offsets, int on_device, void* stream);
+
+/* pbf_sst_scan_size / pbf_sst_scan with the memtables' iterators in front of the tables', as
+ * LsmStorage.scan builds its MergingIterator (lsm_storage.py:184-190): the sources are mts[0..],
+ * then tables[0..], the lowest source index wins a key; segment index q * (nmts + ntables) + u.
+ * Ranges, outputs, capacities, totals, on_device and stream are exactly those of the table calls.
+ * ntables may be 0; nmts == 0 is refused (pbf_sst_scan is that call); nranges * (nmts + ntables) <=
+ * PBF_SCAN_MAX_SEGMENTS.  A memtable range is SSTable.scan's: inclusive at both ends, lower > upper
+ * empty, upper_open = no upper bound.  (The reference's MemTable.scan, memtable.py:81-86 over
+ * red_black_tree.py:56-69, drops in-range keys and is not reproduced: DESIGN.md section 3.) */
+int pbf_mt_scan_size(pbf_memtable_t* const* mts, uint32_t nmts, pbf_sstable_t* const* tables, uint32_t ntables,
+                     const uint8_t* lowers, const uint64_t* lower_offsets, const uint8_t* uppers,
+                     const uint64_t* upper_offsets, const uint8_t* upper_open, uint64_t nranges, uint32_t* seg_lo_out,
+                     uint32_t* seg_hi_out, uint64_t* n_in, uint64_t* key_bytes_in, uint64_t* value_bytes_in);
+int pbf_mt_scan(pbf_memtable_t* const* mts, uint32_t nmts, pbf_sstable_t* const* tables, uint32_t ntables,
+                const uint8_t* lowers, const uint64_t* lower_offsets, const uint8_t* uppers, const uint64_t* upper_offsets,
+                const uint8_t* upper_open, uint64_t nranges, uint8_t* keys_out, uint64_t keys_cap,
+                uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
+                uint64_t offsets_cap, uint64_t* n_out, uint64_t* key_bytes_out, uint64_t* value_bytes_out,
+                uint64_t* range_offsets_out, int on_device, void* stream);
+
+/* LsmStorage._do_flush (lsm_storage.py:193-205) of a resident memtable: pbf_flush_begin without the
+ * upload and the sort, over a device copy of the memtable's run (the memtable stays as it is and may
+ * be destroyed before the job is finished).  An empty memtable is refused as n == 0 is there.  The
+ * job is finished by pbf_job_finish or freed by pbf_job_abort. */
+int pbf_mt_flush_begin(pbf_memtable_t* mt, uint64_t block_size, pbf_job_t** job);
+
 /* Synthetic keys straight into device memory (bench / tests; definitions in
  * pebbledb_amd/keys.py): 16 hex chars of splitmix64(seed + start + i), and the variable-length
  * 8..64-byte family (offsets must already hold the n+1 offsets, relative to offsets[0]).

@@ -110,6 +110,18 @@ SIGNATURES = {
     "pbf_job_abort": (_int, [_vp]),
     "pbf_job_stage_ms": (_int, [_int, _vp]),
     "pbf_sst_read_data": (_int, [_vp, _u8p, _u64]),
+    "pbf_mt_create": (_int, [_int, ctypes.POINTER(_vp)]),
+    "pbf_mt_destroy": (_int, [_vp]),
+    "pbf_mt_apply": (_int, [_vp, _u8p, _vp, _u8p, _vp, _u64]),
+    "pbf_mt_info": (_int, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "pbf_mt_read": (_int, [_vp, _u8p, _u64, _vp, _u8p, _u64, _vp, _u64]),
+    "pbf_mt_get": (_int, [_vp, _u32, _u8p, _vp, _u32, _u64, _int, _vp, _vp, _vp, _vp, _u8p]),
+    "pbf_mt_gather": (_int, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _u64, _u8p, _u64, _vp, _int, _vp]),
+    "pbf_mt_scan_size": (_int, [_vp, _u32, _vp, _u32, _u8p, _vp, _u8p, _vp, _u8p, _u64, _vp, _vp, ctypes.POINTER(_u64),
+                                ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "pbf_mt_scan": (_int, [_vp, _u32, _vp, _u32, _u8p, _vp, _u8p, _vp, _u8p, _u64, _u8p, _u64, _vp, _u8p, _u64, _vp,
+                           _u64, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _int, _vp]),
+    "pbf_mt_flush_begin": (_int, [_vp, _u64, ctypes.POINTER(_vp)]),
     "pbf_gen_splitmix_hex": (_int, [_int, _vp, _u8p, _u64, _u64, _u64]),
     "pbf_gen_varlen": (_int, [_int, _vp, _u8p, _vp, _u64, _u64, _u64]),
     "pbf_last_error": (ctypes.c_char_p, []),

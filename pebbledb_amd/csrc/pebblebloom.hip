@@ -40,6 +40,7 @@
 #include "sstable_merge_kernels.hpp"
 #include "sstable_scan_kernels.hpp"
 #include "memtable_kernels.hpp"
+#include "memtable_read_kernels.hpp"
 
 using namespace pbf;
 
@@ -4413,15 +4414,22 @@ struct ScanSegments {
 
 size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 
+int scan_check_ranges(const ScanArgs& a, uint32_t nsrc, const char* what);
+
 // The checks that need no device: the table list and the ranges.
 int scan_check(pbf_sstable_t* const* tables, uint32_t ntables, const ScanArgs& a) {
     int rc = check_run_tables(tables, ntables, "scan");
     if (rc) return rc;
+    return scan_check_ranges(a, ntables, "tables");
+}
+
+// The ranges of a batch over nsrc sources (`what` they are, for the message).
+int scan_check_ranges(const ScanArgs& a, uint32_t nsrc, const char* what) {
     if (a.nranges == 0) return PBF_OK;
-    if (a.nranges > kScanMaxSegments / ntables)
+    if (a.nranges > kScanMaxSegments / nsrc)
         return fail(PBF_ERR_INVALID, "a scan takes at most " + std::to_string(kScanMaxSegments) +
-                                         " ranges x tables, got " + std::to_string(a.nranges) + " x " +
-                                         std::to_string(ntables));
+                                         " ranges x " + what + ", got " + std::to_string(a.nranges) + " x " +
+                                         std::to_string(nsrc));
     if (!a.lower_offsets || !a.upper_offsets) return fail(PBF_ERR_INVALID, "null pointer");
     for (const uint64_t* o : {a.lower_offsets, a.upper_offsets})
         for (uint64_t q = 0; q < a.nranges; ++q) {
@@ -4437,13 +4445,12 @@ int scan_check(pbf_sstable_t* const* tables, uint32_t ntables, const ScanArgs& a
 // Steps 1 and 2 on `s`: uploads the bounds, k_scan_bounds, the exclusive scan of the counts, and
 // reads N back (one sync).  The caller holds the tables' locks and the context's, and has waited
 // for merge_done.
-int scan_segments(SstCtx& c, hipStream_t s, pbf_sstable_t* const* tables, uint32_t ntables, const ScanArgs& a,
-                  ScanSegments& g) {
-    uint64_t nrec = 0;
-    int rc = fill_merge_set(tables, ntables, g.set, &nrec);
-    if (rc) return rc;
+// `bounds(b, seg_lo, seg_cnt)` launches the door's bounds kernel over nsrc sources per range.
+template <class Bounds>
+int scan_segments_run(SstCtx& c, hipStream_t s, uint32_t nsrc, const ScanArgs& a, ScanSegments& g, Bounds bounds) {
+    int rc;
     const uint64_t Q = a.nranges;
-    g.nseg = Q * ntables;
+    g.nseg = Q * nsrc;
     g.n = 0;
     if (g.nseg == 0) return PBF_OK;
     // bounds: lower offsets ‖ upper offsets ‖ upper_open ‖ lower bytes ‖ upper bytes
@@ -4469,13 +4476,24 @@ int scan_segments(SstCtx& c, hipStream_t s, pbf_sstable_t* const* tables, uint32
     uint64_t* sums = g.seg_base + g.nseg + 1;
     g.seg_lo = reinterpret_cast<uint32_t*>(sums + stiles);
     g.seg_cnt = g.seg_lo + g.nseg;
-    k_scan_bounds<<<grid_for(g.nseg, 256, 1u << 20), 256, 0, s>>>(g.set, b, g.nseg, g.seg_lo, g.seg_cnt);
-    CHECK_LAUNCH();
+    if ((rc = bounds(b, g.seg_lo, g.seg_cnt))) return rc;
     // (a count is below 2^31: the length scan reads it as a non-negative i32)
     if ((rc = len_scan(reinterpret_cast<const int32_t*>(g.seg_cnt), g.nseg, sums, g.seg_base, s))) return rc;
     HIP_TRY(hipMemcpyAsync(&g.n, g.seg_base + g.nseg, 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return PBF_OK;
+}
+
+int scan_segments(SstCtx& c, hipStream_t s, pbf_sstable_t* const* tables, uint32_t ntables, const ScanArgs& a,
+                  ScanSegments& g) {
+    uint64_t nrec = 0;
+    int rc = fill_merge_set(tables, ntables, g.set, &nrec);
+    if (rc) return rc;
+    return scan_segments_run(c, s, ntables, a, g, [&](const ScanBounds& b, uint32_t* seg_lo, uint32_t* seg_cnt) {
+        k_scan_bounds<<<grid_for(g.nseg, 256, 1u << 20), 256, 0, s>>>(g.set, b, g.nseg, seg_lo, seg_cnt);
+        CHECK_LAUNCH();
+        return int(PBF_OK);
+    });
 }
 
 }  // namespace
@@ -5200,6 +5218,605 @@ int pbf_sst_read_data(pbf_sstable_t* t, uint8_t* out_host, uint64_t len) {
     HIP_TRY(hipMemcpyAsync(out_host, t->data.p, len, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return PBF_OK;
+}
+
+}  // extern "C"
+
+// ====================================================================== device memtable
+// A resident, searchable sorted run per memtable (csrc/memtable_read_kernels.hpp): MemTable.put /
+// get and the memtable stage of LsmStorage.get / scan.
+namespace {
+
+struct MtRun {
+    DevBuf keys, ko, vals, vo, prefix;
+    uint64_t n = 0, kb = 0, vb = 0;
+    void release() {
+        for (DevBuf* d : {&keys, &ko, &vals, &vo, &prefix}) d->release();
+        n = kb = vb = 0;
+    }
+    RunView view() const {
+        return RunView{static_cast<const uint8_t*>(keys.p), static_cast<const uint64_t*>(ko.p),
+                       static_cast<const uint8_t*>(vals.p), static_cast<const uint64_t*>(vo.p),
+                       static_cast<const uint64_t*>(prefix.p), n};
+    }
+};
+
+}  // namespace
+
+struct pbf_memtable {
+    int device = 0;
+    std::shared_mutex mu;  // readers hold it shared, pbf_mt_apply and pbf_mt_destroy exclusively
+    MtRun run;
+    std::mutex ev_mu;
+    std::map<hipStream_t, hipEvent_t> users;  // the last asynchronous reader per caller stream
+};
+
+namespace {
+
+// Live handles, as g_sst_live: a call takes a handle's lock only while the handle is listed.
+std::shared_mutex g_mt_mu;
+std::set<pbf_memtable_t*> g_mt_live;
+
+struct MtLocks {
+    std::vector<pbf_memtable_t*> held;
+    int take(pbf_memtable_t* const* ms, uint32_t nm) {
+        if (!ms || nm == 0) return fail(PBF_ERR_INVALID, "no memtables");
+        if (nm > kMtMaxPerCall)
+            return fail(PBF_ERR_INVALID, "a call takes at most " + std::to_string(kMtMaxPerCall) + " memtables, got " +
+                                             std::to_string(nm));
+        std::vector<pbf_memtable_t*> u(ms, ms + nm);
+        std::sort(u.begin(), u.end());
+        if (std::adjacent_find(u.begin(), u.end()) != u.end())
+            return fail(PBF_ERR_INVALID, "the same memtable is listed twice");
+        std::shared_lock<std::shared_mutex> reg(g_mt_mu);
+        for (pbf_memtable_t* m : u)
+            if (!m || !g_mt_live.count(m)) return fail(PBF_ERR_INVALID, "null or destroyed memtable handle");
+        for (pbf_memtable_t* m : u)
+            if (m->device != u[0]->device) return fail(PBF_ERR_INVALID, "all memtables of one call must share a device");
+        for (pbf_memtable_t* m : u) {
+            m->mu.lock_shared();
+            held.push_back(m);
+        }
+        return PBF_OK;
+    }
+    int used_on(hipStream_t s) {
+        for (pbf_memtable_t* m : held) {
+            std::lock_guard<std::mutex> lock(m->ev_mu);
+            hipEvent_t& ev = m->users[s];
+            if (!ev) HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(ev, s));
+        }
+        return PBF_OK;
+    }
+    ~MtLocks() {
+        for (pbf_memtable_t* m : held) m->mu.unlock_shared();
+    }
+};
+
+// The asynchronous readers of a memtable are done (the caller holds its lock exclusively).
+void mt_wait_users(pbf_memtable_t* m) {
+    std::lock_guard<std::mutex> lock(m->ev_mu);
+    for (auto& kv : m->users) (void)hipEventSynchronize(kv.second);
+}
+
+// A run's buffers once its totals are known (RunOut::alloc).
+auto mt_run_alloc(MtRun* r) {
+    return [r](uint64_t n, uint64_t kb, uint64_t vb, RunOut& o) -> int {
+        if (n >= 0xFFFFFFFFull) return fail(PBF_ERR_INVALID, "a memtable holds fewer than 2^32 - 1 records");
+        HIP_TRY(r->keys.ensure(kb + 32));
+        HIP_TRY(r->vals.ensure(vb + 32));
+        HIP_TRY(r->ko.ensure((n + 1) * 8));
+        HIP_TRY(r->vo.ensure((n + 1) * 8));
+        HIP_TRY(r->prefix.ensure((n + 1) * 8));
+        o.keys = static_cast<uint8_t*>(r->keys.p);
+        o.keys_cap = kb;
+        o.values = static_cast<uint8_t*>(r->vals.p);
+        o.values_cap = vb;
+        o.key_offsets = static_cast<uint64_t*>(r->ko.p);
+        o.value_offsets = static_cast<uint64_t*>(r->vo.p);
+        o.offsets_cap = n + 1;
+        return PBF_OK;
+    };
+}
+
+RunOut mt_run_out(MtRun* r, hipStream_t s) {
+    return RunOut{nullptr, 0, nullptr, nullptr, 0, nullptr, 0, &r->n, &r->kb, &r->vb, 1, s, mt_run_alloc(r)};
+}
+
+// prefix[] of a run whose records are queued on s; complete on return.
+int mt_run_prefix(MtRun* r, hipStream_t s) {
+    if (r->n) {
+        k_run_prefix<<<grid_for(r->n, 256, 1u << 20), 256, 0, s>>>(static_cast<const uint8_t*>(r->keys.p),
+                                                                  static_cast<const uint64_t*>(r->ko.p), r->n,
+                                                                  static_cast<uint64_t*>(r->prefix.p));
+        CHECK_LAUNCH();
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return PBF_OK;
+}
+
+// k_src_copy over the sources of `set`, as run_emit launches it.
+auto src_copy_launch(const SrcSet& set, const RunWork& w, hipStream_t s) {
+    return [&set, &w, s](uint64_t* dko, uint64_t* dvo, uint8_t* dk, uint8_t* dv) {
+        k_src_copy<<<grid_for(w.n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(set, w.slots, w.n, w.pos, w.totals, dko, dvo,
+                                                                               dk, dv);
+        CHECK_LAUNCH();
+        return int(PBF_OK);
+    };
+}
+
+// out = the merge of `batch` (first: it wins every shared key) and `old`, both non-empty.
+int mt_merge_runs(int device, const MtRun& batch, const MtRun& old, MtRun* out) {
+    const uint64_t nb = batch.n, na = old.n, n = nb + na;
+    if (n >= 0xFFFFFFFFull) return fail(PBF_ERR_INVALID, "a memtable holds fewer than 2^32 - 1 records");
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    int rc = sst_ctx_stream(c, device);
+    if (rc) return rc;
+    if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
+    hipStream_t s = c.stream;
+    SrcSet set{};
+    set.nm = 2;
+    set.run[0] = batch.view();
+    set.run[1] = old.view();
+    // one range whose windows are the whole runs: seg_base[3] ‖ seg_lo[2] ‖ seg_cnt[2]
+    const uint64_t h_base[3] = {0, nb, n};
+    const uint32_t h_seg[4] = {0, 0, uint32_t(nb), uint32_t(na)};
+    HIP_TRY(c.sseg.ensure(sizeof h_base + sizeof h_seg));
+    auto* seg_base = static_cast<uint64_t*>(c.sseg.p);
+    auto* seg_lo = reinterpret_cast<uint32_t*>(seg_base + 3);
+    HIP_TRY(hipMemcpyAsync(seg_base, h_base, sizeof h_base, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(seg_lo, h_seg, sizeof h_seg, hipMemcpyHostToDevice, s));
+    const RunOut o = mt_run_out(out, s);
+    RunWork w;
+    if ((rc = run_prepare(c, o, n, w))) return rc;
+    k_src_rank<<<grid_for(n, 256, 1u << 20), 256, 0, s>>>(set, seg_base, seg_lo, seg_lo + 2, 2, n, w.slots);
+    CHECK_LAUNCH();
+    SstLocks none;
+    if ((rc = run_emit(c, none, w, o, src_copy_launch(set, w, s), [] { return int(PBF_OK); }))) return rc;
+    return mt_run_prefix(out, s);
+}
+
+// The memtables and tables of one read call, locked shared, as the kernels take them.
+struct MtSources {
+    MtLocks mlocks;
+    SstLocks tlocks;
+    int device = 0;
+    int take(pbf_memtable_t* const* mts, uint32_t nmts, pbf_sstable_t* const* tables, uint32_t ntables,
+             bool distinct_tables = true) {
+        int rc = mlocks.take(mts, nmts);
+        if (rc) return rc;
+        device = mts[0]->device;
+        if (ntables) {
+            if (nmts + ntables > kSstTablesPerLaunch)
+                return fail(PBF_ERR_INVALID, "a call takes at most " + std::to_string(kSstTablesPerLaunch) +
+                                                 " memtables and tables together, got " + std::to_string(nmts + ntables));
+            if (!tables) return fail(PBF_ERR_INVALID, "no tables");
+            if (distinct_tables && (rc = check_run_tables(tables, ntables, "scan"))) return rc;
+            if ((rc = tlocks.take(tables, ntables))) return rc;
+            if (tables[0]->device != device)
+                return fail(PBF_ERR_INVALID, "the memtables and tables of one call must share a device");
+        }
+        return PBF_OK;
+    }
+    int fill(pbf_memtable_t* const* mts, uint32_t nmts, pbf_sstable_t* const* tables, uint32_t ntables, SrcSet& set) {
+        set.nm = nmts;
+        for (uint32_t m = 0; m < nmts; ++m) set.run[m] = mts[m]->run.view();
+        uint64_t nrec = 0;
+        if (ntables) return fill_merge_set(tables, ntables, set.tab, &nrec);
+        set.tab.nt = 0;
+        return PBF_OK;
+    }
+    int used_on(hipStream_t s) {
+        int rc = mlocks.used_on(s);
+        return rc ? rc : tlocks.used_on(s);
+    }
+};
+
+int mt_scan_segments(SstCtx& c, hipStream_t s, const SrcSet& set, const ScanArgs& a, ScanSegments& g) {
+    return scan_segments_run(c, s, set.nm + set.tab.nt, a, g, [&](const ScanBounds& b, uint32_t* seg_lo, uint32_t* seg_cnt) {
+        k_src_bounds<<<grid_for(g.nseg, 256, 1u << 20), 256, 0, s>>>(set, b, g.nseg, seg_lo, seg_cnt);
+        CHECK_LAUNCH();
+        return int(PBF_OK);
+    });
+}
+
+}  // namespace
+
+extern "C" {
+
+int pbf_mt_create(int device, pbf_memtable_t** out) {
+    if (!out) return fail(PBF_ERR_INVALID, "null out pointer");
+    *out = nullptr;
+    int count = 0;
+    HIP_TRY(hipGetDeviceCount(&count));
+    if (device < 0 || device >= count) return fail(PBF_ERR_INVALID, "no such device");
+    pbf_memtable_t* m = new pbf_memtable();
+    m->device = device;
+    std::unique_lock<std::shared_mutex> reg(g_mt_mu);
+    g_mt_live.insert(m);
+    *out = m;
+    return PBF_OK;
+}
+
+int pbf_mt_destroy(pbf_memtable_t* mt) {
+    if (!mt) return PBF_OK;
+    {
+        std::unique_lock<std::shared_mutex> reg(g_mt_mu);
+        if (!g_mt_live.erase(mt)) return fail(PBF_ERR_INVALID, "destroyed or unknown memtable handle");
+    }
+    {
+        std::unique_lock<std::shared_mutex> lock(mt->mu);
+        (void)hipSetDevice(mt->device);
+        mt_wait_users(mt);
+        for (auto& kv : mt->users) (void)hipEventDestroy(kv.second);
+        mt->users.clear();
+        mt->run.release();
+    }
+    delete mt;
+    return PBF_OK;
+}
+
+int pbf_mt_apply(pbf_memtable_t* mt, const uint8_t* keys, const uint64_t* key_offsets, const uint8_t* values,
+                 const uint64_t* value_offsets, uint64_t n) {
+    int device = 0;
+    {
+        std::shared_lock<std::shared_mutex> reg(g_mt_mu);
+        if (!mt || !g_mt_live.count(mt)) return fail(PBF_ERR_INVALID, "null or destroyed memtable handle");
+        device = mt->device;
+    }
+    if (n == 0) return PBF_OK;
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t s = nullptr;
+    int rc = job_stream(device, &s);
+    if (rc) return rc;
+    // the batch's run, as pbf_flush_begin leaves it on the device before planning: uploaded, sorted
+    // and prefixed BEFORE the handle is locked, so readers are shut out for the merge and the swap
+    // only (batches of concurrent applies take effect in the order they get the lock)
+    MtRun batch, merged;
+    auto bail = [&](int code) {
+        const std::string msg = g_last_error;
+        (void)hipStreamSynchronize(s);
+        batch.release();
+        merged.release();
+        return fail(code, msg);
+    };
+    if ((rc = log_sort_run(device, keys, key_offsets, values, value_offsets, n, mt_run_out(&batch, s), nullptr)))
+        return bail(rc);
+    if ((rc = mt_run_prefix(&batch, s))) return bail(rc);
+    {
+        std::shared_lock<std::shared_mutex> reg(g_mt_mu);
+        if (!g_mt_live.count(mt)) return bail(fail(PBF_ERR_INVALID, "null or destroyed memtable handle"));
+        std::unique_lock<std::shared_mutex> lock(mt->mu);
+        reg.unlock();
+        mt_wait_users(mt);  // nobody reads the old run any more
+        if (mt->run.n == 0) {
+            std::swap(mt->run, batch);
+        } else {
+            if ((rc = mt_merge_runs(device, batch, mt->run, &merged))) return bail(rc);
+            std::swap(mt->run, merged);  // (merged now holds the old run: freed below, outside the lock)
+        }
+    }
+    batch.release();
+    merged.release();
+    return PBF_OK;
+}
+
+int pbf_mt_info(pbf_memtable_t* mt, uint64_t* nrecords, uint64_t* key_bytes, uint64_t* value_bytes) {
+    MtLocks locks;
+    int rc = locks.take(&mt, 1);
+    if (rc) return rc;
+    if (nrecords) *nrecords = mt->run.n;
+    if (key_bytes) *key_bytes = mt->run.kb;
+    if (value_bytes) *value_bytes = mt->run.vb;
+    return PBF_OK;
+}
+
+int pbf_mt_read(pbf_memtable_t* mt, uint8_t* keys_out, uint64_t keys_cap, uint64_t* key_offsets_out, uint8_t* values_out,
+                uint64_t values_cap, uint64_t* value_offsets_out, uint64_t offsets_cap) {
+    MtLocks locks;
+    int rc = locks.take(&mt, 1);
+    if (rc) return rc;
+    if (!key_offsets_out || !value_offsets_out) return fail(PBF_ERR_INVALID, "null pointer");
+    const MtRun& r = mt->run;
+    if (r.n + 1 > offsets_cap)
+        return fail(PBF_ERR_INVALID, "the run holds " + std::to_string(r.n) + " records: each offsets array needs " +
+                                         std::to_string(r.n + 1) + " entries, offsets_cap is " + std::to_string(offsets_cap));
+    if (r.kb > keys_cap || (r.kb && !keys_out))
+        return fail(PBF_ERR_INVALID, "the keys need " + std::to_string(r.kb) + " bytes, keys_out holds " +
+                                         std::to_string(keys_out ? keys_cap : 0));
+    if (r.vb > values_cap || (r.vb && !values_out))
+        return fail(PBF_ERR_INVALID, "the values need " + std::to_string(r.vb) + " bytes, values_out holds " +
+                                         std::to_string(values_out ? values_cap : 0));
+    if (r.n == 0) {
+        key_offsets_out[0] = value_offsets_out[0] = 0;
+        return PBF_OK;
+    }
+    HIP_TRY(hipSetDevice(mt->device));
+    hipStream_t s = nullptr;
+    if ((rc = job_stream(mt->device, &s))) return rc;
+    HIP_TRY(hipMemcpyAsync(key_offsets_out, r.ko.p, (r.n + 1) * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(value_offsets_out, r.vo.p, (r.n + 1) * 8, hipMemcpyDeviceToHost, s));
+    if (r.kb) HIP_TRY(hipMemcpyAsync(keys_out, r.keys.p, r.kb, hipMemcpyDeviceToHost, s));
+    if (r.vb) HIP_TRY(hipMemcpyAsync(values_out, r.vals.p, r.vb, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return PBF_OK;
+}
+
+int pbf_mt_get(pbf_memtable_t* const* mts, uint32_t nmts, const uint8_t* keys, const uint64_t* offsets, uint32_t key_len,
+               uint64_t n, int on_device, void* stream, int32_t* src_out, uint64_t* val_off_out, int32_t* val_len_out,
+               uint8_t* miss_mask_out) {
+    MtLocks locks;
+    int rc = locks.take(mts, nmts);
+    if (rc) return rc;
+    if (n == 0) return PBF_OK;
+    if (!src_out || !val_off_out || !val_len_out || !miss_mask_out || (!keys && !offsets))
+        return fail(PBF_ERR_INVALID, "null pointer");
+    if (!offsets && key_len == 0) return fail(PBF_ERR_INVALID, "fixed-width keys need key_len > 0");
+    const int device = mts[0]->device;
+    HIP_TRY(hipSetDevice(device));
+    const uint64_t stride = (n + 7) / 8;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const uint8_t* dk = keys;
+    const uint64_t* dko = offsets;
+    int32_t *dsrc = src_out, *dvl = val_len_out;
+    uint64_t* dvo = val_off_out;
+    uint8_t* dmask = miss_mask_out;
+    std::unique_lock<std::mutex> ctx_lock;
+    if (!on_device) {
+        if (offsets)
+            for (uint64_t i = 0; i < n; ++i) {
+                if (offsets[i + 1] < offsets[i]) return fail(PBF_ERR_INVALID, "key offsets must ascend");
+                if (offsets[i + 1] - offsets[i] > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "a key of 2^31 bytes or more");
+            }
+        SstCtx& c = sst_ctx(device);
+        ctx_lock = std::unique_lock<std::mutex>(c.mu);
+        if ((rc = sst_ctx_stream(c, device))) return rc;
+        s = c.stream;
+        const uint64_t kb = offsets ? offsets[n] - offsets[0] : n * uint64_t(key_len);
+        HIP_TRY(c.keys.ensure(kb + 16));
+        HIP_TRY(c.offs.ensure((n + 1) * 8));
+        HIP_TRY(c.out.ensure(n * 16 + stride + 16));
+        if (kb) HIP_TRY(hipMemcpyAsync(c.keys.p, keys + (offsets ? offsets[0] : 0), kb, hipMemcpyHostToDevice, s));
+        if (offsets) HIP_TRY(hipMemcpyAsync(c.offs.p, offsets, (n + 1) * 8, hipMemcpyHostToDevice, s));
+        dk = static_cast<const uint8_t*>(c.keys.p);
+        dko = offsets ? static_cast<const uint64_t*>(c.offs.p) : nullptr;
+        dvo = static_cast<uint64_t*>(c.out.p);
+        dsrc = reinterpret_cast<int32_t*>(dvo + n);
+        dvl = dsrc + n;
+        dmask = reinterpret_cast<uint8_t*>(dvl + n);
+    }
+    MtSet set{};
+    set.nm = nmts;
+    for (uint32_t m = 0; m < nmts; ++m) set.run[m] = mts[m]->run.view();
+    const Batch b = make_batch(dk, dko, key_len, n);
+    const uint32_t grid = grid_for(n, 256, 1u << 20);
+    if (b.km == kVar)
+        k_mt_get<kVar><<<grid, 256, 0, s>>>(b.ks, n, set, dsrc, dvo, dvl, dmask);
+    else
+        k_mt_get<kFixedN><<<grid, 256, 0, s>>>(b.ks, n, set, dsrc, dvo, dvl, dmask);
+    CHECK_LAUNCH();
+    if (on_device) return locks.used_on(s);
+    HIP_TRY(hipMemcpyAsync(val_off_out, dvo, n * 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(src_out, dsrc, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(val_len_out, dvl, n * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(miss_mask_out, dmask, stride, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return PBF_OK;
+}
+
+int pbf_mt_gather(pbf_memtable_t* const* mts, uint32_t nmts, pbf_sstable_t* const* tables, uint32_t ntables,
+                  const int32_t* where, const uint64_t* val_off, const int32_t* val_len, uint64_t n, uint8_t* out_bytes,
+                  uint64_t out_cap, uint64_t* out_offsets, int on_device, void* stream) {
+    MtSources src;
+    int rc = src.take(mts, nmts, tables, ntables, false);
+    if (rc) return rc;
+    if (!out_offsets || (n && (!where || !val_off || !val_len))) return fail(PBF_ERR_INVALID, "null pointer");
+    const int device = src.device;
+    HIP_TRY(hipSetDevice(device));
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    if ((rc = sst_ctx_stream(c, device))) return rc;
+    hipStream_t s = on_device ? static_cast<hipStream_t>(stream) : c.stream;
+    const int32_t *dw = where, *dvl = val_len;
+    const uint64_t* dvo = val_off;
+    uint64_t* doffs = out_offsets;
+    if (!on_device) {
+        HIP_TRY(c.out.ensure(n * 16 + 16));
+        HIP_TRY(c.offs.ensure((n + 1) * 8));
+        auto* o = static_cast<uint64_t*>(c.out.p);
+        if (n) {
+            HIP_TRY(hipMemcpyAsync(o, val_off, n * 8, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(o + n, where, n * 4, hipMemcpyHostToDevice, s));
+            HIP_TRY(hipMemcpyAsync(reinterpret_cast<int32_t*>(o + n) + n, val_len, n * 4, hipMemcpyHostToDevice, s));
+        }
+        dvo = o;
+        dw = reinterpret_cast<const int32_t*>(o + n);
+        dvl = dw + n;
+        doffs = static_cast<uint64_t*>(c.offs.p);
+    }
+    if (n == 0) {
+        HIP_TRY(hipMemsetAsync(doffs, 0, 8, s));
+    } else {
+        const uint64_t ntiles = (n + kScanTile - 1) / kScanTile;
+        if (ntiles > 0x7FFFFFFFull) return fail(PBF_ERR_INVALID, "batch too large");
+        HIP_TRY(c.tmp.ensure(ntiles * 8));
+        if ((rc = len_scan(dvl, n, static_cast<uint64_t*>(c.tmp.p), doffs, s))) return rc;
+    }
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, doffs + n, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!on_device) HIP_TRY(hipMemcpyAsync(out_offsets, doffs, (n + 1) * 8, hipMemcpyDeviceToHost, s));
+    unsigned int err = 0;
+    if (out_bytes && total) {
+        if (total > out_cap) {
+            HIP_TRY(hipStreamSynchronize(s));
+            return fail(PBF_ERR_INVALID, "the values need " + std::to_string(total) + " bytes, out_bytes holds " +
+                                             std::to_string(out_cap));
+        }
+        uint8_t* dout = out_bytes;
+        if (!on_device) {
+            HIP_TRY(c.gat.ensure(total + 16));
+            dout = static_cast<uint8_t*>(c.gat.p);
+        }
+        HIP_TRY(c.rep.ensure(sizeof(SstReport)));
+        HIP_TRY(hipMemsetAsync(c.rep.p, 0, 4, s));
+        GatherSrc set{};
+        set.nm = nmts;
+        set.nt = ntables;
+        for (uint32_t m = 0; m < nmts; ++m) {
+            set.base[m] = static_cast<const uint8_t*>(mts[m]->run.vals.p);
+            set.len[m] = mts[m]->run.vb;
+        }
+        for (uint32_t t = 0; t < ntables; ++t) {
+            set.base[nmts + t] = static_cast<const uint8_t*>(tables[t]->data.p);
+            set.len[nmts + t] = tables[t]->data_len;
+        }
+        k_src_gather<<<grid_for(n, 256 / kGatherLanes, 1u << 20), 256, 0, s>>>(set, dw, dvo, dvl, n, doffs, dout,
+                                                                               static_cast<unsigned int*>(c.rep.p));
+        CHECK_LAUNCH();
+        HIP_TRY(hipMemcpyAsync(&err, c.rep.p, 4, hipMemcpyDeviceToHost, s));
+        if (!on_device) HIP_TRY(hipMemcpyAsync(out_bytes, dout, total, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (err) return fail(PBF_ERR_INVALID, std::to_string(err) + " entries name no source or lie outside its value bytes");
+    return PBF_OK;
+}
+
+int pbf_mt_scan_size(pbf_memtable_t* const* mts, uint32_t nmts, pbf_sstable_t* const* tables, uint32_t ntables,
+                     const uint8_t* lowers, const uint64_t* lower_offsets, const uint8_t* uppers,
+                     const uint64_t* upper_offsets, const uint8_t* upper_open, uint64_t nranges, uint32_t* seg_lo_out,
+                     uint32_t* seg_hi_out, uint64_t* n_in, uint64_t* key_bytes_in, uint64_t* value_bytes_in) {
+    const ScanArgs a{lowers, uppers, upper_open, lower_offsets, upper_offsets, nranges};
+    MtSources src;
+    int rc = src.take(mts, nmts, tables, ntables);
+    if (rc) return rc;
+    if ((rc = scan_check_ranges(a, nmts + ntables, "sources"))) return rc;
+    if (!n_in || !key_bytes_in || !value_bytes_in) return fail(PBF_ERR_INVALID, "null pointer");
+    const int device = src.device;
+    HIP_TRY(hipSetDevice(device));
+    SrcSet set{};
+    if ((rc = src.fill(mts, nmts, tables, ntables, set))) return rc;
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    if ((rc = sst_ctx_stream(c, device))) return rc;
+    if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
+    hipStream_t s = c.stream;
+    ScanSegments g;
+    if ((rc = mt_scan_segments(c, s, set, a, g))) return rc;
+    unsigned long long tot[kScanSizeTotals] = {0, 0};
+    if (g.n) {
+        HIP_TRY(c.msums.ensure(sizeof tot));
+        auto* totals = static_cast<unsigned long long*>(c.msums.p);
+        HIP_TRY(hipMemsetAsync(totals, 0, sizeof tot, s));
+        k_src_sizes<<<grid_for(g.n, kScanThreads, 4096), kScanThreads, 0, s>>>(set, g.seg_base, g.seg_lo, g.nseg, g.n, totals);
+        CHECK_LAUNCH();
+        HIP_TRY(hipMemcpyAsync(tot, totals, sizeof tot, hipMemcpyDeviceToHost, s));
+    }
+    std::vector<uint32_t> lo;
+    if (g.nseg && (seg_lo_out || seg_hi_out)) {
+        lo.resize(g.nseg);
+        HIP_TRY(hipMemcpyAsync(lo.data(), g.seg_lo, g.nseg * 4, hipMemcpyDeviceToHost, s));
+        if (seg_hi_out) HIP_TRY(hipMemcpyAsync(seg_hi_out, g.seg_cnt, g.nseg * 4, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < lo.size(); ++i) {
+        if (seg_lo_out) seg_lo_out[i] = lo[i];
+        if (seg_hi_out) seg_hi_out[i] += lo[i];  // the count becomes the window's end
+    }
+    *n_in = g.n;
+    *key_bytes_in = tot[0];
+    *value_bytes_in = tot[1];
+    return PBF_OK;
+}
+
+int pbf_mt_scan(pbf_memtable_t* const* mts, uint32_t nmts, pbf_sstable_t* const* tables, uint32_t ntables,
+                const uint8_t* lowers, const uint64_t* lower_offsets, const uint8_t* uppers, const uint64_t* upper_offsets,
+                const uint8_t* upper_open, uint64_t nranges, uint8_t* keys_out, uint64_t keys_cap,
+                uint64_t* key_offsets_out, uint8_t* values_out, uint64_t values_cap, uint64_t* value_offsets_out,
+                uint64_t offsets_cap, uint64_t* n_out, uint64_t* key_bytes_out, uint64_t* value_bytes_out,
+                uint64_t* range_offsets_out, int on_device, void* stream) {
+    const ScanArgs a{lowers, uppers, upper_open, lower_offsets, upper_offsets, nranges};
+    MtSources src;
+    int rc = src.take(mts, nmts, tables, ntables);
+    if (rc) return rc;
+    if ((rc = scan_check_ranges(a, nmts + ntables, "sources"))) return rc;
+    if (!n_out || !key_bytes_out || !value_bytes_out || !key_offsets_out || !value_offsets_out || !range_offsets_out)
+        return fail(PBF_ERR_INVALID, "null pointer");
+    const int device = src.device;
+    HIP_TRY(hipSetDevice(device));
+    SrcSet set{};
+    if ((rc = src.fill(mts, nmts, tables, ntables, set))) return rc;
+    const uint32_t nsrc = nmts + ntables;
+    SstCtx& c = sst_ctx(device);
+    std::lock_guard<std::mutex> lock(c.mu);
+    if ((rc = sst_ctx_stream(c, device))) return rc;
+    if (c.merge_done) HIP_TRY(hipEventSynchronize(c.merge_done));  // the working memory is free again
+    hipStream_t s = on_device ? static_cast<hipStream_t>(stream) : c.stream;
+    ScanSegments g;
+    if ((rc = mt_scan_segments(c, s, set, a, g))) return rc;
+    const RunOut o{keys_out, keys_cap, key_offsets_out, values_out, values_cap, value_offsets_out, offsets_cap,
+                   n_out, key_bytes_out, value_bytes_out, on_device, s};
+    RunWork w;
+    if ((rc = run_prepare(c, o, g.n, w))) return rc;
+    if (w.n) {
+        k_src_rank<<<grid_for(w.n, 256, 1u << 20), 256, 0, s>>>(set, g.seg_base, g.seg_lo, g.seg_cnt, g.nseg, w.n, w.slots);
+        CHECK_LAUNCH();
+    }
+    uint64_t* dro = range_offsets_out;
+    if (!on_device) {
+        HIP_TRY(c.sro.ensure((nranges + 1) * 8));
+        dro = static_cast<uint64_t*>(c.sro.p);
+    }
+    rc = run_emit(c, src.tlocks, w, o, src_copy_launch(set, w, s), [&] {
+        if (w.n) {
+            k_scan_range_offsets<<<grid_for(nranges + 1, 256, 1u << 20), 256, 0, s>>>(g.seg_base, nsrc, nranges, w.slots, w.n,
+                                                                                      w.pos, w.sums, w.totals, dro);
+            CHECK_LAUNCH();
+        } else {
+            HIP_TRY(hipMemsetAsync(dro, 0, (nranges + 1) * 8, s));
+        }
+        if (!on_device) HIP_TRY(hipMemcpyAsync(range_offsets_out, dro, (nranges + 1) * 8, hipMemcpyDeviceToHost, s));
+        return int(PBF_OK);
+    });
+    if (rc) return rc;
+    return on_device ? src.mlocks.used_on(s) : int(PBF_OK);
+}
+
+int pbf_mt_flush_begin(pbf_memtable_t* mt, uint64_t block_size, pbf_job_t** job) {
+    if (!job) return fail(PBF_ERR_INVALID, "null pointer");
+    *job = nullptr;
+    if (block_size == 0 || block_size > kMaxBlockData) return fail(PBF_ERR_INVALID, "block_size must be in (0, 65536]");
+    MtLocks locks;
+    int rc = locks.take(&mt, 1);
+    if (rc) return rc;
+    const MtRun& r = mt->run;
+    if (r.n == 0) return fail(PBF_ERR_INVALID, "an SSTable needs at least one record");
+    pbf_job_t* j = nullptr;
+    if ((rc = job_new(mt->device, true, &j))) return rc;
+    hipStream_t s = nullptr;
+    rc = job_stream(mt->device, &s);
+    auto copy_run = [&]() -> int {  // the job owns its run: a device copy of the memtable's, no upload
+        HIP_TRY(hipEventRecord(j->ev[0], s));
+        HIP_TRY(j->keys.ensure(r.kb + 32));
+        HIP_TRY(j->vals.ensure(r.vb + 32));
+        HIP_TRY(j->ko.ensure((r.n + 1) * 8));
+        HIP_TRY(j->vo.ensure((r.n + 1) * 8));
+        if (r.kb) HIP_TRY(hipMemcpyAsync(j->keys.p, r.keys.p, r.kb, hipMemcpyDeviceToDevice, s));
+        if (r.vb) HIP_TRY(hipMemcpyAsync(j->vals.p, r.vals.p, r.vb, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(j->ko.p, r.ko.p, (r.n + 1) * 8, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(j->vo.p, r.vo.p, (r.n + 1) * 8, hipMemcpyDeviceToDevice, s));
+        j->n = r.n;
+        j->kb = r.kb;
+        j->vb = r.vb;
+        return PBF_OK;
+    };
+    if (!rc) rc = copy_run();
+    // the copies read the memtable's run on s: s is recorded as a user of the run, so an apply or a
+    // destroy waits for them whatever job_plan does (today it ends with a wait for s, n > 0)
+    if (!rc) rc = locks.used_on(s);
+    if (!rc) rc = job_plan(j, s, block_size, 0);
+    return job_publish(j, rc, job);
 }
 
 }  // extern "C"

@@ -163,19 +163,28 @@ def _set_bits(b: int) -> tuple:
 
 
 # ---------------------------------------------------------------------------- get: keys in, values out
-def _walk_device(keys_ptr: int, offsets_ptr: int, key_len: int, n: int, level0, flat, device: int, timings=None):
+def _walk_device(keys_ptr: int, offsets_ptr: int, key_len: int, n: int, level0, flat, device: int, timings=None,
+                 memtables=()):
     """The whole batched get on device memory (torch tensors hold the buffers): the filter and
     key-range stage in their device-pointer forms (``probe_multi_device``,
     ``pbf_key_range_mask`` with on_device=1), so the candidate masks never leave the GPU, then
     ``pbf_sst_get`` and ``pbf_sst_gather``, all ordered on torch's current stream.  Returns device
     tensors (table int32[n], values uint8[total], value_offsets int64[n+1], val_len int32[n]).
-    `timings`: a dict that receives HIP-event times of the three stages in ms."""
+    `timings`: a dict that receives HIP-event times of the three stages in ms.
+    With `memtables` the memtable stage (``pbf_mt_get``) runs first on the same stream; its miss
+    mask is ANDed into every table's candidate mask, so a key a memtable answered is searched in
+    no table, and ``pbf_mt_gather`` packs the values of both kinds of hit (timings: memtable_ms)."""
     import torch
 
     from .sstable_read import _handles
 
     tables = list(level0) + list(flat)
-    hs = _handles(tables)
+    memtables = list(memtables)
+    hs = _handles(tables) if tables else None
+    mts = None
+    if memtables:
+        from .device_memtable import _mt_handles
+        mts = _mt_handles(memtables)
     n0, T, nb = len(level0), len(tables), (n + 7) // 8
     dev = torch.device("cuda", device)
     vp = ctypes.c_void_p
@@ -190,6 +199,15 @@ def _walk_device(keys_ptr: int, offsets_ptr: int, key_len: int, n: int, level0, 
             return e
 
         masks = torch.zeros((T, nb), dtype=torch.uint8, device=dev)
+        em = mark()
+        if mts is not None:  # lsm_storage.py:154-162: the memtables answer first
+            msrc = torch.empty(n, dtype=torch.int32, device=dev)
+            mvo = torch.empty(n, dtype=torch.int64, device=dev)
+            mvl = torch.empty(n, dtype=torch.int32, device=dev)
+            miss = torch.empty(nb, dtype=torch.uint8, device=dev)
+            rc = L.pbf_mt_get(mts, len(memtables), vp(keys_ptr), vp(offsets_ptr or None), key_len, n, 1, vp(sp or None),
+                              vp(msrc.data_ptr()), vp(mvo.data_ptr()), vp(mvl.data_ptr()), vp(miss.data_ptr()))
+            _native.check(rc, "pbf_mt_get")
         e0 = mark()
         if level0:
             f0 = [t.bloom_filter for t in level0]
@@ -212,32 +230,51 @@ def _walk_device(keys_ptr: int, offsets_ptr: int, key_len: int, n: int, level0, 
                                offsets_ptr)
             fl[0].signal_stream(sp)
             masks[n0:] &= rng  # lsm_storage.py:173-175: in range, then may_contain
+        if mts is not None and T:
+            masks &= miss  # a key a memtable holds is searched in no table
         e1 = mark()
-        table = torch.empty(n, dtype=torch.int32, device=dev)
-        val_off = torch.empty(n, dtype=torch.int64, device=dev)
-        val_len = torch.empty(n, dtype=torch.int32, device=dev)
-        mp = (vp * T)(*[masks[t].data_ptr() for t in range(T)])
-        rc = L.pbf_sst_get(hs, T, vp(keys_ptr), vp(offsets_ptr or None), key_len, n, mp, 1, vp(sp or None),
-                           vp(table.data_ptr()), vp(val_off.data_ptr()), vp(val_len.data_ptr()))
-        _native.check(rc, "pbf_sst_get")
+        if T:
+            table = torch.empty(n, dtype=torch.int32, device=dev)
+            val_off = torch.empty(n, dtype=torch.int64, device=dev)
+            val_len = torch.empty(n, dtype=torch.int32, device=dev)
+            mp = (vp * T)(*[masks[t].data_ptr() for t in range(T)])
+            rc = L.pbf_sst_get(hs, T, vp(keys_ptr), vp(offsets_ptr or None), key_len, n, mp, 1, vp(sp or None),
+                               vp(table.data_ptr()), vp(val_off.data_ptr()), vp(val_len.data_ptr()))
+            _native.check(rc, "pbf_sst_get")
+        if mts is not None:  # table[i] = -2 - m for a hit in memtable m
+            hit = msrc >= 0
+            table = torch.where(hit, -2 - msrc, table) if T else torch.where(hit, -2 - msrc, msrc)
+            val_off = torch.where(hit, mvo, val_off) if T else mvo
+            val_len = torch.where(hit, mvl, val_len) if T else mvl
         e2 = mark()
         total = int(val_len.clamp(min=0).sum(dtype=torch.int64).item())
         offs = torch.empty(n + 1, dtype=torch.int64, device=dev)
         vals = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)
         e3 = mark()
-        rc = L.pbf_sst_gather(hs, T, vp(table.data_ptr()), vp(val_off.data_ptr()), vp(val_len.data_ptr()), n,
-                              vp(vals.data_ptr()) if total else None, total, vp(offs.data_ptr()), 1, vp(sp or None))
-        _native.check(rc, "pbf_sst_gather")
+        if mts is not None:
+            rc = L.pbf_mt_gather(mts, len(memtables), hs, T, vp(table.data_ptr()), vp(val_off.data_ptr()),
+                                 vp(val_len.data_ptr()), n, vp(vals.data_ptr()) if total else None, total,
+                                 vp(offs.data_ptr()), 1, vp(sp or None))
+            _native.check(rc, "pbf_mt_gather")
+        else:
+            rc = L.pbf_sst_gather(hs, T, vp(table.data_ptr()), vp(val_off.data_ptr()), vp(val_len.data_ptr()), n,
+                                  vp(vals.data_ptr()) if total else None, total, vp(offs.data_ptr()), 1, vp(sp or None))
+            _native.check(rc, "pbf_sst_gather")
         e4 = mark()
         cur.synchronize()
         if timings is not None:
             timings.update(filter_ms=e0.elapsed_time(e1), walk_ms=e1.elapsed_time(e2), gather_ms=e3.elapsed_time(e4))
+            if mts is not None:
+                timings.update(memtable_ms=em.elapsed_time(e0))
     return table, vals[:total], offs, val_len
 
 
-def get_batch(keys, level0, levels):
-    """``LsmStorage.get`` with empty memtables for a batch of keys (lsm_storage.py:164-179), keys in,
-    values out: (table int32[n], values uint8[], value_offsets uint64[n+1]).  table[i] is the row
+def get_batch(keys, level0, levels, memtables=()):
+    """``LsmStorage.get`` for a batch of keys (lsm_storage.py:153-179), keys in, values out: (table
+    int32[n], values uint8[], value_offsets uint64[n+1]).  `memtables` = [active, *immutables]
+    (``DeviceMemTable``s, at most 16, on the tables' device) are searched first, in that order;
+    ``memtables=()`` is the get with empty memtables.  table[i] is ``-2 - m`` when memtable m
+    answered key i (a stored empty value is an answer), otherwise the row
     (``candidate_masks``' numbering: L0 newest first, then level by level) of the SSTable whose
     value the reference returns for key i, -1 when it returns None; value i =
     values[value_offsets[i]:value_offsets[i+1]] (empty when absent, and for a stored empty value,
@@ -250,13 +287,18 @@ def get_batch(keys, level0, levels):
     level0 = list(level0)
     flat = [t for lvl in levels for t in lvl]
     tables = level0 + flat
+    memtables = list(memtables)
     n = pk.n
-    if n == 0 or not tables:
+    if n == 0 or not (tables or memtables):
         return np.full(n, -1, dtype=np.int32), np.zeros(0, dtype=np.uint8), np.zeros(n + 1, dtype=np.uint64)
     devs = {t.device for t in tables}
     if len(devs) > 1:
         raise ValueError(f"all tables of one call must share a device, got devices {sorted(devs)}")
-    device = tables[0].device
+    if len(memtables) > 16:  # PBF_MT_MAX_PER_CALL
+        raise ValueError(f"a call takes at most 16 memtables, got {len(memtables)}")
+    if len(devs | {m.device for m in memtables}) > 1:
+        raise ValueError("the memtables and tables of one call must share a device")
+    device = (tables or memtables)[0].device
     dev = torch.device("cuda", device)
     def upload(a):  # (torch wants a writable array: packed keys may view an immutable bytes object)
         return torch.from_numpy(a if a.flags.writeable else a.copy()).to(dev)
@@ -264,12 +306,12 @@ def get_batch(keys, level0, levels):
     kd = upload(pk.data if pk.data.size else np.zeros(1, np.uint8))
     od = None if pk.offsets is None else upload(pk.offsets.view(np.int64))
     table, vals, offs, _ = _walk_device(kd.data_ptr(), 0 if od is None else od.data_ptr(), pk.key_len, n, level0, flat,
-                                        device)
+                                        device, memtables=memtables)
     return table.cpu().numpy(), vals.cpu().numpy(), offs.cpu().numpy().view(np.uint64)
 
 
-def get_many(keys, level0, levels) -> list:
-    """[LsmStorage.get(key) for key in keys] with empty memtables: bytes, or None."""
-    table, vals, offs = get_batch(keys, level0, levels)
+def get_many(keys, level0, levels, memtables=()) -> list:
+    """[LsmStorage.get(key) for key in keys] (`memtables` as in ``get_batch``): bytes, or None."""
+    table, vals, offs = get_batch(keys, level0, levels, memtables)
     raw = vals.tobytes()
-    return [raw[int(offs[i]):int(offs[i + 1])] if table[i] >= 0 else None for i in range(len(table))]
+    return [raw[int(offs[i]):int(offs[i + 1])] if table[i] != -1 else None for i in range(len(table))]
